@@ -15,6 +15,12 @@ the only exchange step the path has.  Candidate shards are disjoint index ranges
 (weak scaling).  Inputs are generated on the device (nothing crosses PCIe inside
 the timed region).
 
+A plain run sets up (compiles the query's kernels, picks the faster tier), warms up, times the K
+steps and prints the line.  ``--dump-outputs DIR`` also writes what the last timed step returned
+(``first_hit_index.npy``, ``hit_count.npy``).  ``--full`` adds the legs measured beside the headline
+figure after the timed steps (``jit_asm_tier``, the ``time_to_first_model*`` searches,
+``dropin_stream``, ``roofline_eval``, ``cpu_baseline``); without it those keys are null.
+
 roofline: achieved = VALU lane-instructions per candidate MEASURED by rocprofv3
 (SQ_INSTS_VALU x 64 / candidates, committed under profiles/ by tools/profile.sh and
 matched to this exact kernel by the SHA of its JIT source) x C / the search kernel's
@@ -65,12 +71,19 @@ def parse():
                          "per GPU, so the per-step host sync and the RCCL exchange stay ~1 %% of a step "
                          "at 8 GPUs)")
     ap.add_argument("--seed", type=int, default=0x6D797468)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beside the headline figure: the first tier's own "
+                         "rate, the time-to-first-model searches, the get_model stream, the eval-kernel rooflines "
+                         "and the CPU baseline (each can be dropped again with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float64): "
+                         "first_hit_index (-1: no hit) and hit_count")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample time")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-stream", action="store_true", help="skip the LASER-shaped get_model stream")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-stream", action="store_true", help="--full: skip the LASER-shaped get_model stream")
     ap.add_argument("--no-ttfm", action="store_true",
-                    help="skip the time-to-first-model searches (profiling passes: full launches only)")
-    ap.add_argument("--no-eval", action="store_true", help="skip the eval-kernel roofline (roofline_eval)")
+                    help="--full: skip the time-to-first-model searches and the first tier's own rate")
+    ap.add_argument("--no-eval", action="store_true", help="--full: skip the eval-kernel roofline (roofline_eval)")
     ap.add_argument("--eval-candidates", type=int, default=1 << 22,
                     help="candidates per eval launch (HBM-resident SoA; C2: 1,241 B each)")
     ap.add_argument("--eval-only", action="store_true",
@@ -230,9 +243,10 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     total_hits = 0
+    last = None
     for s in range(args.warmup, args.warmup + args.steps):
-        _, nh = step(s)
-        total_hits += nh
+        last = step(s)
+        total_hits += last[1]
     torch.cuda.synchronize()
     if distributed:
         dist.barrier()
@@ -247,11 +261,20 @@ def main():
     dt = float(dt_t.item())
     kernel_ms = float(km_t.item())
 
+    # what the last timed step handed its caller: the lowest satisfying index of its sweep (after the
+    # exchange under a launcher) and this rank's hit count; the same arguments sweep the same
+    # candidates (seed and window are functions of the arguments alone), so two builds compare 1:1
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_dir = Path(args.dump_outputs)
+        dump_dir.mkdir(parents=True, exist_ok=True)
+        np.save(dump_dir / "first_hit_index.npy", np.array([-1 if last[0] is None else last[0]], dtype=np.float64))
+        np.save(dump_dir / "hit_count.npy", np.array([last[1]], dtype=np.float64))
+
     # the JIT's first tier (gfx950 assembly emitted by the engine, jit_asm.cpp): its cold compile (comgr's
     # cache off) and its rate at 2^28 candidates per launch on this workload; the product runs it from a
     # few ms after a query's first miss until the O3 kernel above is ready
     asm_tier = None
-    if rank == 0 and args.engine == "jit" and not args.no_ttfm:
+    if args.full and rank == 0 and args.engine == "jit" and not args.no_ttfm:
         prev_cc = os.environ.get("AMD_COMGR_CACHE")
         os.environ["AMD_COMGR_CACHE"] = "0"
         t1 = time.perf_counter()
@@ -284,7 +307,7 @@ def main():
     ttfm_breakdown = None
     ttfm_cold_ms = None
     ttfm_cold_breakdown = None
-    if rank == 0 and not args.no_ttfm:
+    if args.full and rank == 0 and not args.no_ttfm:
         # cold: a fresh flatten cache (the query is new to the process), nothing pooled for it yet
         from mythril_amd import ssa as _ssa
 
@@ -314,7 +337,7 @@ def main():
     # (interpreter first, async JIT compile, compiled kernel); "cold" compiles the kernel inside the
     # timing, "warm" finds it in the code cache (the same query asked again)
     hard = None
-    if rank == 0 and not args.no_ttfm:
+    if args.full and rank == 0 and not args.no_ttfm:
         hroots = hard_query(cs, HARD_BITS.get(args.workload, 24))
         search.FLATTEN_CACHE = ssa.FlattenCache(aux_words=True)
         search._GEN_CACHE.clear()
@@ -347,7 +370,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t1 = time.perf_counter()
-    if args.no_ttfm:
+    if not args.full or args.no_ttfm:
         ttfm_index = None
     elif distributed:
         ttfm_index, _ = sharded_first_hit(first_hit, rank, world, 1 << 20, max_epochs=1024, device="cuda")
@@ -362,7 +385,7 @@ def main():
     # the drop-in under a LASER-shaped stream of this workload's queries through solver.get_model,
     # 200 ms budget each (tools/stream_bench.py; async JIT compile inside the budget), rank 0
     stream = None
-    if rank == 0 and world == 1 and inproc == 1 and not args.no_stream:
+    if args.full and rank == 0 and world == 1 and inproc == 1 and not args.no_stream:
         sys.path.insert(0, str(Path(__file__).resolve().parent / "tools"))
         import stream_bench
 
@@ -385,7 +408,7 @@ def main():
 
     # the eval kernel's own roofline (unspecialised C2 and C4 programs on HBM-resident SoA inputs)
     evals = None
-    if rank == 0 and world == 1 and inproc == 1 and not args.no_eval:
+    if args.full and rank == 0 and world == 1 and inproc == 1 and not args.no_eval:
         evals = []
         # the O3 and first-tier (jit_asm.cpp) eval kernels, each on the [row][candidate] SoA and on the
         # tiled SoA (MG_JIT_SOA_TILED: a group's rows in one block)
@@ -403,7 +426,7 @@ def main():
 
     # CPU baseline: the C restatement over a bounded sample of the same candidates
     cpu = None
-    if rank == 0 and world == 1 and inproc == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and inproc == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(P, blob, args, eng, prog, gh, jit, tier)
 
     if rank == 0:

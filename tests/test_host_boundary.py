@@ -229,6 +229,20 @@ def test_bench_gpus_without_launcher_needs_the_devices():
     assert r.stdout == ""
 
 
+def test_bench_plain_run_is_the_default(monkeypatch):
+    """``--full`` (the legs beside the headline figure) and ``--dump-outputs`` are off unless asked for."""
+    import sys
+
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs) == (True, "d")
+
+
 def test_model_from_assignment_matches_model_from_sites():
     """The model read back from mg_search's assign_out rows (literal site keys and AUX-sliced
     calldata bytes filled in on the host, ``search._model_layout``) equals the generic

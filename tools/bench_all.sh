@@ -8,6 +8,9 @@ for W in ${@:-suicide_kill token_transfer_underflow etherstore_reentrancy bectok
   N=268435456; [ "$W" = sha3_keyed_mapping ] && N=16777216
   bash tools/profile.sh $W jit $N || exit 1
   cp gpurun_out/prof_$W/pmc_$W.json gpurun_out/pmc_$W.json
-  timeout -k 10 300 python bench.py --workload $W --candidates $N --pmc-dir gpurun_out --no-stream --no-eval > gpurun_out/b_$W.json 2> gpurun_out/b_$W.err || { tail -5 gpurun_out/b_$W.err; exit 1; }
-  cat gpurun_out/b_$W.json >> gpurun_out/bench_all.jsonl
+  # --full: the time-to-first-model searches and the CPU baseline belong to each workload's line.
+  # O: the directory this run writes to (the one holding the bench_all.jsonl emptied above)
+  O=$(dirname $(ls -t */bench_all.jsonl | head -1))
+  timeout -k 10 300 python bench.py --full --workload $W --candidates $N --pmc-dir $O --no-stream --no-eval > $O/b_$W.json 2> $O/b_$W.err || { tail -5 $O/b_$W.err; exit 1; }
+  cat $O/b_$W.json >> $O/bench_all.jsonl
 done
