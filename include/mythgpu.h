@@ -19,6 +19,9 @@
  *   mg_search                 Optimize.check() for SAT instances
  *                             (mythril/support/model.py:44,
  *                             solver.py:47-57): first satisfying candidate index
+ *   mg_search_batch           the per-bucket Optimize.check() calls of the independence solver
+ *                             (mythril/laser/smt/solver/independence_solver.py:119-140):
+ *                             several different queries in one interpreter launch
  *   mg_eval / mg_eval_generated
  *                             ModelRef.eval(expr, model_completion=True)
  *                             (mythril/laser/smt/model.py:45-59) batched over
@@ -285,6 +288,28 @@ int mg_eval_generated(uint64_t prog, uint64_t gen, uint64_t seed, uint64_t start
  * watch_words uint32: the model read-back of Solver.model(), laser/smt/solver/solver.py:59-64) */
 int mg_search(uint64_t prog, uint64_t gen, uint64_t seed, uint64_t start, uint64_t count, uint32_t flags,
               uint64_t* first_hit, uint64_t* n_hits, uint32_t* assign_out);
+
+/* n different searches in one call: entry q sweeps [start, start + count) of generator `gen` of
+ * program `prog` under `seed`, and res[q] / reqs[q].assign_out (nullable) are what
+ * mg_search(prog, gen, seed, start, count, flags, ...) would return for it: first_hit exact in
+ * every mode, n_hits equal without MG_SEARCH_EARLY_EXIT (with it, counts depend on timing).
+ * The same (prog, gen) may appear in several entries; count = 0 gives {UINT64_MAX, 0}; n = 0
+ * returns MG_OK.  Every handle is checked before anything is queued: one bad entry fails the
+ * whole call with MG_E_INVALID and nothing is launched.
+ * Latency-bound entries (a window of at most two waves per CU, a value file of at most 255
+ * words per lane: the first launch of a get_model query) share interpreter launches of up to 64
+ * entries each — one kernel, each block running its entry's program — with one wait for all hit
+ * buffers and one for the models of the entries that hit; every other entry is served by the
+ * mg_search path inside the same call.  The variable-disjoint buckets of one query
+ * (mythril/laser/smt/solver/independence_solver.py:119-140) are the first user. */
+typedef struct mg_search_req {
+  uint64_t prog, gen, seed, start, count;
+  uint32_t* assign_out;
+} mg_search_req_t;
+typedef struct mg_search_res {
+  uint64_t first_hit, n_hits;
+} mg_search_res_t;
+int mg_search_batch(uint32_t n, const mg_search_req_t* reqs, uint32_t flags, mg_search_res_t* res);
 
 /* ---- JIT specialisation (comgr; hipRTC fallback) -----------------------
  * The compiler runs in a helper process (mythgpu_jitd, next to the library; started on the

@@ -177,15 +177,16 @@ __device__ __forceinline__ Instr ld_instr(const KArgs& k, uint32_t pc) {
 // ---------------------------------------------------------------------------
 struct VFLds {
   uint32_t* base;
-  __device__ VFLds(uint32_t* lds, const KArgs&) : base(lds) {}
+  __device__ VFLds(uint32_t* lds, const KArgs&, uint32_t) : base(lds) {}
   __device__ __forceinline__ uint32_t& at(uint32_t w) const { return base[w * kWave + threadIdx.x]; }
 };
 
 struct VFGlobal {
   uint32_t* base;
   uint64_t stride;
-  __device__ VFGlobal(uint32_t*, const KArgs& k)
-      : base(k.scratch + (uint64_t)blockIdx.x * kWave + threadIdx.x), stride(k.stride) {}
+  // vb: the block's id within its launch (run_body.inc)
+  __device__ VFGlobal(uint32_t*, const KArgs& k, uint32_t vb)
+      : base(k.scratch + (uint64_t)vb * kWave + threadIdx.x), stride(k.stride) {}
   __device__ __forceinline__ uint32_t& at(uint32_t w) const { return base[(uint64_t)w * stride]; }
 };
 
@@ -527,7 +528,7 @@ struct VFG {
 
 template <class VF, int MODE, int TIER, int KG>
 __device__ __forceinline__ void run_program(const KArgs& k, const VF& vf0, const uint64_t* i, const GKeys* key,
-                                            bool early, const bool* active, uint32_t* verdict) {
+                                            bool early, const bool* active, uint32_t* verdict, uint32_t vb) {
 _Pragma("unroll")
   for (int g = 0; g < KG; g++) verdict[g] = 1;
   const uint32_t n_instr = k.n_instr;
@@ -852,7 +853,7 @@ _Pragma("unroll")
           // capture launch (one group per block, KG = 1): every lane's watch rows, [block][row][lane],
           // so the first hit's model is read back without a second program pass
           const VFG<VF, KG> vf{vf0, 0};
-          uint32_t* w = k.watch + ((uint64_t)blockIdx.x * k.watch_words + in.p0) * kWave + threadIdx.x;
+          uint32_t* w = k.watch + ((uint64_t)vb * k.watch_words + in.p0) * kWave + threadIdx.x;
           for (uint32_t j = 0; j < L; j++) w[(uint64_t)j * kWave] = vf.at(in.a + j);
         }
         break;
@@ -870,112 +871,83 @@ __global__ void __launch_bounds__(256) k_gather_rows(const uint32_t* __restrict_
   if (r < rows) dst[r] = src[(uint64_t)r * kWave];
 }
 
+// The interpreter's block body lives in run_body.inc and is included into k_run and k_run_batch
+// with MG_VB / MG_VGRID, the block's id and the grid size of the launch it belongs to: the
+// physical ones here, the entry's own in k_run_batch.  An include and not a __forceinline__
+// function: as a function the body is optimised once on its own and again inside the kernel, and
+// ten k_run instantiations then changed their register allocation.
 template <class VF, int MODE, int TIER, int KG>
 __global__ void __launch_bounds__(kWave) k_run(KArgs k) {
-  VF vf0(mg_lds, k);
-  // the generator constants into LDS behind the value file (one wave per block: its own later
-  // reads see the writes, LDS runs a wave's operations in order)
-  if (MODE != MODE_EVAL && k.lds_g != kNoLds)
-    for (uint32_t i = threadIdx.x; i < k.n_gconsts; i += kWave) mg_lds[k.lds_g + i] = cst(k.gconsts)[i];
-  // EVAL sweeps rows [0, count); GEN / SEARCH sweep the aligned 64-index groups that
-  // cover [start, start + count), one group per wave (the GEN3 group key is per wave)
-  const uint64_t a0 = (MODE == MODE_EVAL) ? 0ull : (k.start & ~63ull);
-  const uint64_t end = k.start + k.count;
-  const uint64_t total = (MODE == MODE_EVAL) ? k.count : (end - a0);
-  // KG groups per wave per pass (run_program): a wave's pass covers KG * 64 consecutive indices
-  const uint64_t step = (uint64_t)gridDim.x * kWave * KG;
-  const bool early = (MODE == MODE_SEARCH) && (k.flags & MG_SEARCH_EARLY_EXIT);
-  uint64_t wave_best = ~0ull, wave_hits = 0;  // wave-uniform; published once per wave
-  // idx & 63 == threadIdx.x & 63 below (a0 and base are multiples of 64): the lane half of
-  // the GEN3 lane key is fixed per thread
-  const uint64_t lk = (MODE == MODE_EVAL) ? 0ull : gen_lane_key(threadIdx.x & 63u, k.sk);
-  // Warm the scalar cache with the program and the generator specs, 64-byte lines eight loads at a
-  // time: a wave reads them with dependent scalar loads, one instruction (32 B) or spec ahead, so a
-  // cold cache costs it an L2 round trip every other instruction — the floor of an easy query's time
-  // to first model, which one wave's pass over the program is.
-  if (k.flags & kFlagPrefetch) {
-    uint32_t acc = 0;
-    auto warm = [&acc](const uint32_t* base, uint32_t lines) {
-      const auto* b = cst(base);
-      for (uint32_t l = 0; l < lines; l += 8) {
-        uint32_t x[8];
-#pragma unroll
-        for (int q = 0; q < 8; q++) x[q] = (l + q < lines) ? b[16u * (l + q)] : 0u;
-#pragma unroll
-        for (int q = 0; q < 8; q++) acc ^= x[q];
-      }
-    };
-    warm((const uint32_t*)k.code, min((k.n_instr + 2u) / 2u, 512u));
-    if (MODE != MODE_EVAL && k.specs) warm((const uint32_t*)k.specs, min((k.n_specs + 1u) / 2u, 512u));
-    if (acc == 0x5EED1E55u && k.count == ~0ull) k.hits[0] = acc;  // never true: keeps the loads
+#define MG_VB blockIdx.x
+#define MG_VGRID gridDim.x
+#include "run_body.inc"
+#undef MG_VB
+#undef MG_VGRID
+}
+
+// One entry of a batched search launch (mg_search_batch): the arguments of one query's SEARCH
+// launch and the run of physical blocks [block0, block0 + nblocks) that sweeps it.  Entries are in
+// block order and cover the grid without gaps.
+struct alignas(64) BatchEntry {
+  KArgs k;
+  uint32_t block0, nblocks;
+};
+
+// N different (program, generator, seed, window) searches in one launch: every block finds its
+// entry and runs it exactly as k_run<VFLds, MODE_SEARCH, TIER, 1> would in a grid of the entry's
+// nblocks blocks.  The block id is an SGPR and the table is read through the constant address
+// space, so the search and the entry's KArgs are scalar work: the program fetch, the generator
+// specs and the opcode switch stay wave-uniform, as with kernel arguments.
+template <int TIER>
+__global__ void __launch_bounds__(kWave) k_run_batch(const BatchEntry* tab, uint32_t n) {
+  const auto* t = cst(tab);
+  const uint32_t b = blockIdx.x;
+  // the last entry whose first block is at or below b (n <= kManySlots: six steps)
+  uint32_t lo = 0, hi = n;
+  while (lo + 1 < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (t[mid].block0 <= b) lo = mid;
+    else hi = mid;
   }
-  // the hoisted literals: their slots are never reused, so once per thread is enough
-  for (uint32_t pc = 0; pc < k.pc0; pc++) {
-    const Instr in = ld_instr(k, pc);
-    const uint32_t L = (in.wd + 31) >> 5;
-    const auto* c = cst(k.consts) + in.p0;
-    MG_FOR_G(MG_LIMBS(L, vf.at(in.dst + j) = c[j];););
-  }
-  for (uint64_t base = (uint64_t)blockIdx.x * kWave * KG; base < total; base += step) {
-    bool active[KG];
-    uint64_t i[KG];
-    GKeys key[KG];
-#pragma unroll
-    for (int g = 0; g < KG; g++) {
-      const uint64_t off = base + (uint64_t)g * kWave + threadIdx.x;
-      const uint64_t idx = a0 + off;  // candidate index (GEN / SEARCH)
-      active[g] = (MODE == MODE_EVAL) ? off < total : (idx >= k.start && idx < end);
-      // EVAL: SoA row; GEN: output row (only written by active lanes)
-      i[g] = (MODE == MODE_EVAL) ? (active[g] ? off : total - 1) : (idx - k.start);
-    }
-    uint64_t cur_u = ~0ull;  // the hit word as this group starts (early exit only)
-    if (early) {
-      // every candidate below the current first hit is still evaluated, so the
-      // final minimum is exact; waves entirely above it stop
-      const unsigned long long cur = read_first_hit(k.first_hit, k.flags);
-      // readfirstlane returns int: widen through uint32_t, or a low word with bit 31 set would
-      // sign-extend over the high word
-      cur_u = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(cur >> 32)) << 32) |
-              (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)cur);
-      if (a0 + base >= cur_u) break;
-    }
-    // each group's key from its base (a0 + base + 64 g, a multiple of 64: idx >> 6 is the same for
-    // every lane), so the compiler sees G as wave-uniform: the MIXED alternatives are scalar branches
-    // and the generator specs scalar loads (from idx, G looked per-lane: divergent branches, vector loads)
-#pragma unroll
-    for (int g = 0; g < KG; g++) key[g] = MODE != MODE_EVAL ? gen_keys_lk(a0 + base + (uint64_t)g * kWave, lk, k.sg) : GKeys{};
-    uint32_t v[KG];
-    run_program<VF, MODE, TIER, KG>(k, vf0, i, key, early, active, v);
-#pragma unroll
-    for (int g = 0; g < KG; g++) {
-      v[g] = active[g] ? v[g] : 0u;
-      if (MODE == MODE_SEARCH) {
-        const unsigned long long m = __ballot(v[g] != 0);
-        if (m) {
-          const uint64_t first = a0 + base + (uint64_t)g * kWave + (uint64_t)(__ffsll((long long)m) - 1);
-          wave_hits += (uint64_t)__popcll(m);
-          if (first < wave_best) {
-            wave_best = first;
-            // (a hit at or above the word read as the group started cannot lower it: no atomic)
-            if (early && threadIdx.x == 0 && first < cur_u) {
-              atomicMin(k.first_hit, (unsigned long long)first);
-              publish_peers(k.first_hit, (unsigned long long)first);
-            }
-          }
-        }
-      } else if (active[g]) {
-        k.verdict[i[g]] = (uint8_t)v[g];
-      }
-    }
-  }
-  if (MODE == MODE_SEARCH && threadIdx.x == 0) {
-    // a first hit that cannot lower the current minimum is not published; the count goes to the
-    // block's stripe (kHitStripes)
-    if (wave_best != ~0ull &&
-        wave_best < read_first_hit(k.first_hit, k.flags))
-      atomicMin(k.first_hit, (unsigned long long)wave_best);
-    if (wave_hits) atomicAdd(k.hits + kHitStride * (1u + (blockIdx.x % kHitStripes)) - 1u, (unsigned long long)wave_hits);
-  }
+  const uint32_t q = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
+  if (q >= n) return;
+  const auto* ent = t + q;
+  const uint32_t vb = b - ent->block0, vgrid = ent->nblocks;
+  if (vb >= vgrid) return;  // a block past the table's last entry
+  KArgs k;
+  k.code = ent->k.code;
+  k.consts = ent->k.consts;
+  k.aux = ent->k.aux;
+  k.specs = ent->k.specs;
+  k.gconsts = ent->k.gconsts;
+  k.coord_width = ent->k.coord_width;
+  k.soa = nullptr;
+  k.verdict = nullptr;
+  k.watch = ent->k.watch;
+  k.scratch = nullptr;
+  k.first_hit = ent->k.first_hit;
+  k.hits = ent->k.hits;
+  k.start = ent->k.start;
+  k.count = ent->k.count;
+  k.seed = ent->k.seed;
+  k.stride = 0;
+  k.sk = ent->k.sk;
+  k.sg = ent->k.sg;
+  k.n_instr = ent->k.n_instr;
+  k.value_words = ent->k.value_words;
+  k.flags = ent->k.flags;
+  k.watch_words = ent->k.watch_words;
+  k.n_specs = ent->k.n_specs;
+  k.pc0 = ent->k.pc0;
+  k.n_gconsts = ent->k.n_gconsts;
+  k.lds_g = kNoLds;
+  using VF = VFLds;
+  constexpr int MODE = MODE_SEARCH, KG = 1;
+#define MG_VB vb
+#define MG_VGRID vgrid
+#include "run_body.inc"
+#undef MG_VB
+#undef MG_VGRID
 }
 
 // batched concrete Keccak-256: one lane per message
@@ -1223,6 +1195,13 @@ struct Engine {
   unsigned long long* h_hitmany = nullptr;
   hipStream_t xs[4] = {};
   hipEvent_t xev[4] = {};
+  // mg_search_batch: the entry table of one k_run_batch launch (pinned image and device copy,
+  // kManySlots entries) and the staging rows of the hit entries' models (device, pinned)
+  BatchEntry* h_btab = nullptr;
+  BatchEntry* d_btab = nullptr;
+  uint32_t* d_bstage = nullptr;
+  uint32_t* h_bstage = nullptr;
+  size_t bstage_words = 0;
   mg_stats_t stats{};
   uint64_t refused_base = 0;  // jit_refused_total() at the last mg_stats_reset
 };
@@ -1547,6 +1526,22 @@ static int collect_hits(Engine& e, mg_stats_t& st, uint64_t count, unsigned long
   return MG_OK;
 }
 
+// the kManySlots hit buffers of the batched entry points (mg_jit_search_many, mg_search_batch),
+// their pinned armed image / read-back and the launch streams, created on first use
+static int ensure_hitmany(Engine& e) {
+  if (e.d_hitmany) return MG_OK;
+  HIPCHK(hipMalloc((void**)&e.d_hitmany, (size_t)kManySlots * kHitAlloc * sizeof(unsigned long long)));
+  HIPCHK(hipHostMalloc((void**)&e.h_hitmany, 2 * (size_t)kManySlots * kHitAlloc * sizeof(unsigned long long),
+                       hipHostMallocDefault));
+  std::memset(e.h_hitmany, 0, 2 * (size_t)kManySlots * kHitAlloc * sizeof(unsigned long long));
+  for (uint32_t q = 0; q < kManySlots; q++) e.h_hitmany[(size_t)q * kHitAlloc] = ~0ull;  // armed; peer count 0
+  for (int q = 0; q < kManyStreams; q++) {
+    HIPCHK(hipStreamCreateWithFlags(&e.xs[q], hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&e.xev[q], hipEventDisableTiming));
+  }
+  return MG_OK;
+}
+
 template <int MODE>
 static int launch(Engine& e, DevProgram& p, KArgs k, uint64_t count) {
   if (count == 0) return MG_OK;
@@ -1726,6 +1721,10 @@ static int warm_kernels(Engine& e) {
   warm_run<MODE_EVAL>(e);
   warm_run<MODE_GEN>(e);
   warm_run<MODE_SEARCH>(e);
+  // the batched search (an empty table: every block returns before it reads an entry)
+  hipLaunchKernelGGL((k_run_batch<kTierLight>), dim3(1), dim3(kWave), 0, e.stream, (const BatchEntry*)nullptr, 0u);
+  hipLaunchKernelGGL((k_run_batch<kTierMid>), dim3(1), dim3(kWave), 0, e.stream, (const BatchEntry*)nullptr, 0u);
+  hipLaunchKernelGGL((k_run_batch<kTierHeavy>), dim3(1), dim3(kWave), 0, e.stream, (const BatchEntry*)nullptr, 0u);
   hipLaunchKernelGGL(k_gather_rows, dim3(1), dim3(256), 0, e.stream, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0u);
   hipLaunchKernelGGL(k_keccak, dim3(1), dim3(256), 0, e.stream, (const uint8_t*)nullptr, (const uint64_t*)nullptr,
                      (const uint32_t*)nullptr, (uint64_t)0, (uint8_t*)nullptr);
@@ -1977,6 +1976,13 @@ static void free_dev_buffers(Engine& e) {
   if (e.h_hitmany) (void)hipHostFree(e.h_hitmany);
   e.d_hitmany = nullptr;
   e.h_hitmany = nullptr;
+  if (e.d_btab) (void)hipFree(e.d_btab);
+  if (e.h_btab) (void)hipHostFree(e.h_btab);
+  if (e.d_bstage) (void)hipFree(e.d_bstage);
+  if (e.h_bstage) (void)hipHostFree(e.h_bstage);
+  e.d_btab = e.h_btab = nullptr;
+  e.d_bstage = e.h_bstage = nullptr;
+  e.bstage_words = 0;
   for (int q = 0; q < 4; q++) {
     if (e.xs[q]) (void)hipStreamDestroy(e.xs[q]);
     if (e.xev[q]) (void)hipEventDestroy(e.xev[q]);
@@ -2400,11 +2406,10 @@ static int read_assignment(Engine& e, DevGen& g, uint64_t seed, uint64_t idx, ui
   return MG_OK;
 }
 
-int mg_search(uint64_t prog, uint64_t gen, uint64_t seed, uint64_t start, uint64_t count, uint32_t flags,
-              uint64_t* first_hit, uint64_t* n_hits, uint32_t* assign_out) {
-  Engine& e = E();
-  std::lock_guard<std::mutex> g(e.mu);
-  OnDevice od_(e);
+// mg_search with e.mu held and the primary device current (mg_search_batch serves the entries it
+// cannot batch through it)
+static int search_locked(Engine& e, uint64_t prog, uint64_t gen, uint64_t seed, uint64_t start, uint64_t count,
+                         uint32_t flags, uint64_t* first_hit, uint64_t* n_hits, uint32_t* assign_out) {
   DevProgram* p = find_prog(e, prog);
   if (!p) return set_err(MG_E_INVALID, "bad program handle");
   auto it = e.gens.find(gen);
@@ -2529,6 +2534,206 @@ int mg_search(uint64_t prog, uint64_t gen, uint64_t seed, uint64_t start, uint64
   if (n_hits) *n_hits = res[1];
   e.stats.hits += res[1];
   if (assign_out && res[0] != ~0ull) return read_assignment(e, *it->second, seed, res[0], assign_out);
+  return MG_OK;
+}
+
+int mg_search(uint64_t prog, uint64_t gen, uint64_t seed, uint64_t start, uint64_t count, uint32_t flags,
+              uint64_t* first_hit, uint64_t* n_hits, uint32_t* assign_out) {
+  Engine& e = E();
+  std::lock_guard<std::mutex> g(e.mu);
+  OnDevice od_(e);
+  return search_locked(e, prog, gen, seed, start, count, flags, first_hit, n_hits, assign_out);
+}
+
+// an entry mg_search_batch can put into a k_run_batch launch: a latency-bound window (at most two
+// waves per CU, launch_async's bound, so every block sweeps one 64-index group), on the primary
+// device, with the value file of the search program in one block's LDS
+static bool batchable(const Engine& e, const DevGen& dg, uint64_t start, uint64_t count) {
+  if (count == 0 || split_over_devices(count) || !dg.spec.uploaded || dg.spec.low.value_words > 255u) return false;
+  const uint64_t lanes = (start + count) - (start & ~63ull);
+  return lanes <= (uint64_t)std::max(e.cu_count, 1) * 2u * kWave;
+}
+
+// entries reqs[idx[0 .. m)] (m <= kManySlots, all batchable) as one k_run_batch launch: one wait for
+// the hit buffers, then the models of the captured hits gathered into one staging buffer and read
+// back with one copy (the second wait); a hit that was not captured gets its model from
+// read_assignment
+static int search_batch_launch(Engine& e, const mg_search_req_t* reqs, uint32_t flags, const uint32_t* idx, uint32_t m,
+                               mg_search_res_t* res) {
+  if (int rc = ensure_hitmany(e)) return rc;
+  if (!e.d_btab) {
+    HIPCHK(hipMalloc((void**)&e.d_btab, (size_t)kManySlots * sizeof(BatchEntry)));
+    HIPCHK(hipHostMalloc((void**)&e.h_btab, (size_t)kManySlots * sizeof(BatchEntry), hipHostMallocDefault));
+  }
+  if (!e.d_capture) {
+    HIPCHK(hipMalloc((void**)&e.d_capture, kCaptureBytes));
+    e.capture_bytes = kCaptureBytes;
+  }
+  static const bool prefetch = [] {
+    const char* g = getenv("MYTHGPU_INTERP_PREFETCH");
+    return !(g && g[0] == '0');
+  }();
+  struct Slot {
+    DevGen* dg;
+    bool capture;
+    uint32_t ww;
+    size_t cap_off;  // words into d_capture
+  } sl[kManySlots];
+  uint32_t blocks = 0;
+  size_t cap_words = 0, shmem = 0, stage_words = 0;
+  int tier = kTierLight;
+  uint64_t total = 0;
+  for (uint32_t s = 0; s < m; s++) {
+    const mg_search_req_t& r = reqs[idx[s]];
+    DevGen& dg = *e.gens.at(r.gen);
+    const uint32_t ww = dg.spec_watch.low.watch_words;
+    const uint64_t lanes = (r.start + r.count) - (r.start & ~63ull);
+    const uint32_t nb = (uint32_t)((lanes + kWave - 1) / kWave);
+    // capture: the entry runs the watch-list variant and every lane's watch rows go to the entry's
+    // own slice of d_capture, [virtual block][row][lane]; the slices follow each other
+    const size_t need = (size_t)nb * ww * kWave;
+    const bool capture = r.assign_out && ww && dg.spec_watch.uploaded && dg.spec_watch.low.value_words <= 255u &&
+                         (cap_words + need) * 4u <= kCaptureBytes;
+    DevProgram& p = capture ? dg.spec_watch : dg.spec;
+    sl[s] = Slot{&dg, capture, ww, cap_words};
+    BatchEntry& be = e.h_btab[s];
+    be = BatchEntry{};
+    KArgs& k = be.k;
+    k.code = p.d_code;
+    k.consts = p.d_consts;
+    k.aux = p.d_aux;
+    k.coord_width = p.d_coord_width;
+    k.specs = dg.d_specs;
+    k.gconsts = dg.d_consts;
+    k.n_gconsts = (uint32_t)dg.consts.size();
+    k.first_hit = e.d_hitmany + (size_t)s * kHitAlloc;
+    k.hits = k.first_hit + 1;
+    k.start = r.start;
+    k.count = r.count;
+    k.seed = r.seed;
+    k.sk = seed_lane_key(r.seed);
+    k.sg = seed_group_key(r.seed);
+    k.n_instr = (uint32_t)p.low.code.size();
+    k.value_words = p.low.value_words;
+    k.n_specs = p.low.n_coords;
+    k.pc0 = p.low.n_hoisted;
+    k.flags = flags | (prefetch ? kFlagPrefetch : 0u);
+    k.lds_g = kNoLds;
+    if (capture) {
+      k.watch = e.d_capture + cap_words;
+      k.watch_words = ww;
+      cap_words += need;
+      stage_words += ww;
+    }
+    be.block0 = blocks;
+    be.nblocks = nb;
+    blocks += nb;
+    shmem = std::max(shmem, (size_t)p.low.value_words * kWave * 4);
+    tier = std::max(tier, p.tier);
+    total += r.count;
+  }
+  if (stage_words > e.bstage_words) {
+    if (e.d_bstage) (void)hipFree(e.d_bstage);
+    if (e.h_bstage) (void)hipHostFree(e.h_bstage);
+    e.d_bstage = e.h_bstage = nullptr;
+    e.bstage_words = 0;
+    const size_t cap = std::max<size_t>(stage_words, 4096);
+    HIPCHK(hipMalloc((void**)&e.d_bstage, cap * 4));
+    HIPCHK(hipHostMalloc((void**)&e.h_bstage, cap * 4, hipHostMallocDefault));
+    e.bstage_words = cap;
+  }
+  const size_t hit_bytes = (size_t)m * kHitAlloc * sizeof(unsigned long long);
+  unsigned long long* back = e.h_hitmany + (size_t)kManySlots * kHitAlloc;
+  HIPCHK(hipMemcpyAsync(e.d_hitmany, e.h_hitmany, hit_bytes, hipMemcpyHostToDevice, e.stream));
+  HIPCHK(hipMemcpyAsync(e.d_btab, e.h_btab, (size_t)m * sizeof(BatchEntry), hipMemcpyHostToDevice, e.stream));
+  HIPCHK(hipEventRecord(e.ev0, e.stream));
+  const dim3 g(blocks), b(kWave);
+  // one launch at the highest tier among the entries: a higher tier's handlers are a superset
+  if (tier == kTierHeavy) hipLaunchKernelGGL((k_run_batch<kTierHeavy>), g, b, shmem, e.stream, e.d_btab, m);
+  else if (tier == kTierMid) hipLaunchKernelGGL((k_run_batch<kTierMid>), g, b, shmem, e.stream, e.d_btab, m);
+  else hipLaunchKernelGGL((k_run_batch<kTierLight>), g, b, shmem, e.stream, e.d_btab, m);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(e.ev1, e.stream));
+  HIPCHK(hipMemcpyAsync(back, e.d_hitmany, hit_bytes, hipMemcpyDeviceToHost, e.stream));
+  HIPCHK(hipEventRecord(e.ev2, e.stream));
+  HIPCHK(hipEventSynchronize(e.ev2));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, e.ev0, e.ev1));
+  e.stats.launches++;
+  e.stats.last_kernel_ms = ms;
+  e.stats.kernel_ms_total += ms;
+  e.stats.candidates += total;
+  e.stats.last_candidates = total;
+  size_t staged = 0;
+  for (uint32_t s = 0; s < m; s++) {
+    const mg_search_req_t& r = reqs[idx[s]];
+    const unsigned long long* h = back + (size_t)s * kHitAlloc;
+    uint64_t nh = h[1];
+    for (uint32_t t = 1; t <= kHitStripes; t++) nh += h[kHitStride * t];
+    res[idx[s]].first_hit = h[0];
+    res[idx[s]].n_hits = nh;
+    e.stats.hits += nh;
+    if (h[0] == ~0ull || !sl[s].capture) continue;
+    // the hit's virtual block (one group per block, in order) and lane: its column of the slice
+    const uint64_t off = h[0] - (r.start & ~63ull);
+    const uint32_t ww = sl[s].ww;
+    const uint32_t* src = e.d_capture + sl[s].cap_off + ((off / kWave) * ww) * kWave + off % kWave;
+    hipLaunchKernelGGL(k_gather_rows, dim3((ww + 255) / 256), dim3(256), 0, e.stream, src, e.d_bstage + staged, ww);
+    staged += ww;
+  }
+  if (staged) {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(e.h_bstage, e.d_bstage, staged * 4, hipMemcpyDeviceToHost, e.stream));
+    HIPCHK(hipStreamSynchronize(e.stream));
+    size_t at = 0;
+    for (uint32_t s = 0; s < m; s++) {
+      if (res[idx[s]].first_hit == ~0ull || !sl[s].capture) continue;
+      std::memcpy(reqs[idx[s]].assign_out, e.h_bstage + at, (size_t)sl[s].ww * 4);
+      at += sl[s].ww;
+    }
+  }
+  for (uint32_t s = 0; s < m; s++) {
+    const mg_search_req_t& r = reqs[idx[s]];
+    if (res[idx[s]].first_hit == ~0ull || sl[s].capture || !r.assign_out) continue;
+    if (int rc = read_assignment(e, *sl[s].dg, r.seed, res[idx[s]].first_hit, r.assign_out)) return rc;
+  }
+  return MG_OK;
+}
+
+int mg_search_batch(uint32_t n, const mg_search_req_t* reqs, uint32_t flags, mg_search_res_t* res) {
+  if (n == 0) return MG_OK;
+  Engine& e = E();
+  std::lock_guard<std::mutex> g(e.mu);
+  if (!e.init) return set_err(MG_E_NOTINIT, "mg_init not called");
+  if (!reqs || !res) return set_err(MG_E_INVALID, "mg_search_batch: null array");
+  OnDevice od_(e);
+  // every entry is checked before anything is queued: one bad entry fails the whole call
+  for (uint32_t q = 0; q < n; q++) {
+    auto it = e.gens.find(reqs[q].gen);
+    if (!find_prog(e, reqs[q].prog)) return set_err(MG_E_INVALID, "mg_search_batch: bad program handle in entry " + std::to_string(q));
+    if (it == e.gens.end() || it->second->prog != reqs[q].prog)
+      return set_err(MG_E_INVALID, "mg_search_batch: bad generator handle in entry " + std::to_string(q));
+  }
+  std::vector<uint32_t> in_batch, alone;
+  for (uint32_t q = 0; q < n; q++) {
+    res[q].first_hit = ~0ull;
+    res[q].n_hits = 0;
+    (batchable(e, *e.gens.at(reqs[q].gen), reqs[q].start, reqs[q].count) ? in_batch : alone).push_back(q);
+  }
+  for (size_t b0 = 0; b0 < in_batch.size(); b0 += kManySlots) {
+    const uint32_t m = (uint32_t)std::min<size_t>(kManySlots, in_batch.size() - b0);
+    if (int rc = search_batch_launch(e, reqs, flags, in_batch.data() + b0, m, res)) return rc;
+  }
+  // everything else (empty, large or multi-device windows, value files past one block's LDS)
+  // through the single-query path, inside the same call
+  for (uint32_t q : alone) {
+    uint64_t fh = ~0ull, nh = 0;
+    if (int rc = search_locked(e, reqs[q].prog, reqs[q].gen, reqs[q].seed, reqs[q].start, reqs[q].count, flags, &fh, &nh,
+                               reqs[q].assign_out))
+      return rc;
+    res[q].first_hit = fh;
+    res[q].n_hits = nh;
+  }
   return MG_OK;
 }
 
@@ -3316,17 +3521,7 @@ int mg_jit_search_many(uint64_t jit, uint32_t n, const uint64_t* seeds, const ui
   if (!find_prog(e, j.prog) || git == e.gens.end() || !j.fsearch) return set_err(MG_E_INVALID, "jit was not compiled for search");
   for (uint32_t q = 0; q < n; q++)
     if (counts[q] > (1ull << 52)) return set_err(MG_E_INVALID, "mg_jit_search_many: more than 2^52 candidates in one launch");
-  if (!e.d_hitmany) {
-    HIPCHK(hipMalloc((void**)&e.d_hitmany, (size_t)kManySlots * kHitAlloc * sizeof(unsigned long long)));
-    HIPCHK(hipHostMalloc((void**)&e.h_hitmany, 2 * (size_t)kManySlots * kHitAlloc * sizeof(unsigned long long),
-                         hipHostMallocDefault));
-    std::memset(e.h_hitmany, 0, 2 * (size_t)kManySlots * kHitAlloc * sizeof(unsigned long long));
-    for (uint32_t q = 0; q < kManySlots; q++) e.h_hitmany[(size_t)q * kHitAlloc] = ~0ull;  // armed; peer count 0
-    for (int q = 0; q < kManyStreams; q++) {
-      HIPCHK(hipStreamCreateWithFlags(&e.xs[q], hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&e.xev[q], hipEventDisableTiming));
-    }
-  }
+  if (int rc = ensure_hitmany(e)) return rc;
   const uint32_t* gconsts = git->second->d_consts;
   for (uint32_t b0 = 0; b0 < n; b0 += kManySlots) {
     const uint32_t m = std::min<uint32_t>(kManySlots, n - b0);

@@ -51,7 +51,7 @@ EXPORTS = [
     "mg_init", "mg_collective_kind", "mg_shutdown", "mg_last_error", "mg_version", "mg_program_check", "mg_program_check_gen",
     "mg_program_specialized", "mg_program_load",
     "mg_program_info", "mg_program_free", "mg_gen_load", "mg_gen_info", "mg_gen_free", "mg_eval", "mg_eval_dev",
-    "mg_eval_generated", "mg_search", "mg_keccak256", "mg_stats", "mg_stats_reset", "mg_dev_alloc",
+    "mg_eval_generated", "mg_search", "mg_search_batch", "mg_keccak256", "mg_stats", "mg_stats_reset", "mg_dev_alloc",
     "mg_dev_free", "mg_dev_upload", "mg_dev_download", "mg_program_jit_source", "mg_program_jit_asm", "mg_code_object_check", "mg_jit_compile", "mg_jit_compile_ex", "mg_jit_verdicts", "mg_jit_info", "mg_jit_layout",
     "mg_jit_compile_async", "mg_jit_poll", "mg_jit_cancel", "mg_jit_helper_pid", "mg_cache_clear", "mg_split_range",
     "mg_jit_free", "mg_jit_search", "mg_jit_search_many", "mg_jit_eval", "mg_jit_eval_dev",
@@ -84,6 +84,17 @@ class Stats(C.Structure):
         ("last_candidates", C.c_uint64), ("device", C.c_uint32), ("cu_count", C.c_uint32),
         ("clock_mhz", C.c_uint32), ("n_devices", C.c_uint32), ("jit_refused", C.c_uint64),
     ]
+
+
+class SearchReq(C.Structure):
+    _fields_ = [
+        ("prog", C.c_uint64), ("gen", C.c_uint64), ("seed", C.c_uint64), ("start", C.c_uint64),
+        ("count", C.c_uint64), ("assign_out", C.POINTER(C.c_uint32)),
+    ]
+
+
+class SearchRes(C.Structure):
+    _fields_ = [("first_hit", C.c_uint64), ("n_hits", C.c_uint64)]
 
 
 _lib = None
@@ -131,6 +142,7 @@ def load_library(path: Optional[Path] = None) -> C.CDLL:
             "mg_eval_generated": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, u8p, u32p]),
             "mg_search": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                     u64p, u64p, u32p]),
+            "mg_search_batch": (C.c_int, [C.c_uint32, C.POINTER(SearchReq), C.c_uint32, C.POINTER(SearchRes)]),
             "mg_keccak256": (C.c_int, [u8p, u32p, C.c_uint64, u8p]),
             "mg_stats": (C.c_int, [C.POINTER(Stats)]),
             "mg_stats_reset": (C.c_int, []),
@@ -391,6 +403,23 @@ class Engine:
         ap = _ptr(assign, C.c_uint32) if assign is not None else None
         _check(self.lib.mg_search(prog, gen, seed, start, count, flags, C.byref(fh), C.byref(nh), ap))
         return (None if fh.value == NO_HIT else fh.value), nh.value
+
+    def search_batch(self, reqs, early_exit: bool = True):
+        """Several searches in one call (``mg_search_batch``): ``reqs`` is a sequence of
+        ``(prog, gen, seed, start, count, assign or None)``; returns ``[(first hit or None, hits)]``
+        in order, each what :meth:`search` returns for the same arguments (with ``early_exit`` the
+        hit counts depend on timing).  ``assign`` (contiguous uint32[watch_words]) gets a hit's watch rows."""
+        n = len(reqs)
+        arr = (SearchReq * max(n, 1))()
+        for q, (prog, gen, seed, start, count, assign) in enumerate(reqs):
+            if assign is not None and (assign.dtype != np.uint32 or not assign.flags["C_CONTIGUOUS"]):
+                raise ValueError("search_batch: assign must be a contiguous uint32 array")
+            arr[q] = SearchReq(prog, gen, seed, start, count,
+                               _ptr(assign, C.c_uint32) if assign is not None else None)
+        res = (SearchRes * max(n, 1))()
+        flags = MG_SEARCH_EARLY_EXIT if early_exit else 0
+        _check(self.lib.mg_search_batch(n, arr, flags, res))
+        return [(None if res[q].first_hit == NO_HIT else int(res[q].first_hit), int(res[q].n_hits)) for q in range(n)]
 
     # JIT-specialised kernels --------------------------------------
     def jit_compile(self, prog: int, gen: int = 0, gen_verdicts: bool = False, asm: bool = False,

@@ -449,10 +449,15 @@ LAST_ENGINE = None
 LAST_RESULT = None
 
 
+def _next_chunk(chunk: int, compiled: bool) -> int:
+    """The launch size that follows a launch of ``chunk`` candidates without a hit."""
+    return min(chunk * (16 if chunk < (1 << 16) else 4), 1 << 30 if compiled else 1 << 26)
+
+
 def search(engine, roots: Sequence[T.Term], seed: int = 0x6D797468, chunk: int = 1 << 12,
            max_candidates: int = 1 << 26, timeout_s: float = 10.0, gen: Optional[GenBuilder] = None,
            want_model: bool = True, jit: str = "auto", jit_cost_s: Optional[float] = None,
-           cancel=None, max_launch_s: Optional[float] = None) -> SearchResult:
+           cancel=None, max_launch_s: Optional[float] = None, start: int = 0) -> SearchResult:
     """Find the lowest-index satisfying candidate (or give up: None).
 
     ``jit``: "never" keeps the generic interpreter (``k_run``, no compile latency);
@@ -468,14 +473,19 @@ def search(engine, roots: Sequence[T.Term], seed: int = 0x6D797468, chunk: int =
     launch) and are capped by the measured rate so that a launch ends inside the budget
     (and inside ``max_launch_s``).  ``cancel`` (a ``threading.Event``) is checked before
     every launch: the hook sets it when z3 answered first (``plugin._race``).
-    The model comes back with the hit (``mg_search``'s ``assign_out``)."""
+    The model comes back with the hit (``mg_search``'s ``assign_out``).
+
+    ``start`` > 0 resumes the index stream there, as a search whose first launch of ``chunk``
+    candidates covered ``[0, start)`` and missed (``search_many`` made that launch for several
+    queries at once): ``start`` candidates count as scanned, the next launch has the size that
+    follows ``chunk`` and the JIT tiers are submitted as after a first miss."""
     tp = time.perf_counter()
     P, blob = prepare(roots, gen)
     th = time.perf_counter()
     prog = engine.load(P.to_bytes())
     t0 = time.perf_counter()
     timing = {"host_prepare_ms": (th - tp) * 1e3}
-    scanned = 0
+    scanned = start
     hit = None
     hits = 0
     used = "interp"
@@ -502,7 +512,8 @@ def search(engine, roots: Sequence[T.Term], seed: int = 0x6D797468, chunk: int =
                     used, tier = "jit", "o3"
                 except Exception:  # the JIT rejected this program: scan on the interpreter
                     jit = "never"
-            start = 0
+            if start:
+                chunk = _next_chunk(chunk, jh is not None)
             while scanned < max_candidates:
                 now = time.perf_counter()
                 left = timeout_s - (now - t0)
@@ -612,7 +623,7 @@ def search(engine, roots: Sequence[T.Term], seed: int = 0x6D797468, chunk: int =
                 # with one group per block the engine captures the hit's model in the same pass
                 # (mg_search); then geometric growth amortises the launch + sync per chunk
                 # (x16 after the 2^12 capture launch: a query that misses there is not an easy one)
-                chunk = min(chunk * (16 if chunk < (1 << 16) else 4), 1 << 26 if jh is None else 1 << 30)
+                chunk = _next_chunk(chunk, jh is not None)
         finally:
             if race is not None:
                 engine.jit_free(race["asm"])
@@ -642,27 +653,102 @@ def search(engine, roots: Sequence[T.Term], seed: int = 0x6D797468, chunk: int =
     return res
 
 
-def search_partitioned(engine, roots: Sequence[T.Term], timeout_s: float = 10.0, **kw) -> SearchResult:
+def search_many(engine, queries: Sequence[Sequence[T.Term]], seed: int = 0x6D797468, chunk: int = 1 << 12,
+                max_candidates: int = 1 << 26, timeout_s: float = 10.0, gen: Optional[GenBuilder] = None,
+                want_model: bool = True, cancel=None, stop_at_give_up: bool = False, **kw) -> List[SearchResult]:
+    """``search`` for several independent queries, their first launches as ONE engine call
+    (``mg_search_batch``: one interpreter launch sweeps ``[0, chunk)`` of every query and captures
+    the models of those that hit).  A query that hit there is finished; one that missed continues
+    through ``search(..., start=chunk)``, exactly where a serial search stands after its first
+    launch missed.  First hit and model of every query equal what ``search`` alone returns.
+
+    Budgets and ``cancel`` are checked before the batch and before each continuation; a query that
+    is not reached gets a result without an index.  ``stop_at_give_up``: after the first query that
+    gives up the remaining continuations are skipped (``search_partitioned`` needs every bucket)."""
+    t0 = time.perf_counter()
+
+    def gave_up(scanned=0):
+        return SearchResult(None, 0, scanned, time.perf_counter() - t0)
+
+    def stopped():
+        return timeout_s - (time.perf_counter() - t0) <= 0 or (cancel is not None and cancel.is_set())
+
+    queries = list(queries)
+    n = min(chunk, max_candidates)
+    if not queries:
+        return []
+    if stopped() or n <= 0:
+        return [gave_up() for _ in queries]
+    prepared = [prepare(q, gen) for q in queries]
+    th = time.perf_counter()
+    assigns = [np.zeros(max(P.watch_words, 1), dtype=np.uint32) if want_model else None for P, _ in prepared]
+    handles = []
+    try:
+        for P, blob in prepared:
+            handles.append([engine.load(P.to_bytes()), None])
+            handles[-1][1] = engine.load_gen(handles[-1][0], blob)
+        tl = time.perf_counter()
+        first = engine.search_batch([(h[0], h[1], seed, 0, n, a) for h, a in zip(handles, assigns)], early_exit=True)
+    finally:
+        for prog, gh in handles:
+            if gh is not None:
+                engine.free_gen(gh)
+            engine.free(prog)
+    t1 = time.perf_counter()
+    out: List[SearchResult] = []
+    skip = False
+    global LAST_ENGINE, LAST_RESULT
+    for q, (P, _), a, (idx, nh) in zip(queries, prepared, assigns, first):
+        if idx is not None:
+            r = SearchResult(idx, nh, n, t1 - t0)
+            r.timing = {"host_prepare_ms": (th - t0) * 1e3, "load_ms": (tl - th) * 1e3, "search_ms": (t1 - th) * 1e3,
+                        "batched": len(queries)}
+            if want_model:
+                r.model = (1,) + model_from_assignment(P, a) + (P,)
+            LAST_ENGINE, LAST_RESULT = "interp", r
+        elif skip or stopped() or n >= max_candidates:
+            r = gave_up(n)
+        else:
+            r = search(engine, q, seed=seed, chunk=chunk, max_candidates=max_candidates,
+                       timeout_s=timeout_s - (time.perf_counter() - t0), gen=gen, want_model=want_model,
+                       cancel=cancel, start=n, **kw)
+        skip = skip or (stop_at_give_up and r.index is None)
+        out.append(r)
+    return out
+
+
+def search_partitioned(engine, roots: Sequence[T.Term], timeout_s: float = 10.0, batch: Optional[bool] = None,
+                       **kw) -> SearchResult:
     """Search each variable-disjoint bucket (``partition.py``) on its own and merge
     the bucket models (``independence_solver.py:119-140``).  ``index`` is the
     tuple of per-bucket first hits; the model tuple is
-    ``(verdict, scalars, arrays, funcs, [programs])``."""
+    ``(verdict, scalars, arrays, funcs, [programs])``.
+
+    ``batch=True`` (or ``MYTHGPU_BATCH=1`` when ``batch`` is None) sends the buckets' first launches
+    to the engine as one call (``search_many``) instead of one search after the other; the result is
+    the same either way.  Default: off."""
     from .partition import partition
 
     buckets = partition(roots)
     if len(buckets) <= 1:
         return search(engine, roots, timeout_s=timeout_s, **kw)
+    if batch is None:
+        batch = os.environ.get("MYTHGPU_BATCH", "0") == "1"
     t0 = time.perf_counter()
     idx, hits, scanned = [], 0, 0
     ver, scalars, arrays, funcs, progs = 1, {}, {}, {}, []
     engines = set()
+    many = iter(search_many(engine, buckets, timeout_s=timeout_s, stop_at_give_up=True, **kw)) if batch else None
     for b in buckets:
         left = timeout_s - (time.perf_counter() - t0)
-        if left <= 0 or (kw.get("cancel") is not None and kw["cancel"].is_set()):
+        if many is not None:
+            r = next(many)
+        elif left <= 0 or (kw.get("cancel") is not None and kw["cancel"].is_set()):
             res = SearchResult(None, 0, scanned, time.perf_counter() - t0)
             res.buckets = len(buckets)
             return res
-        r = search(engine, b, timeout_s=left, **kw)
+        else:
+            r = search(engine, b, timeout_s=left, **kw)
         scanned += r.scanned
         engines.add(getattr(r, "engine", "interp"))
         if r.index is None:
