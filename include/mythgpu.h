@@ -22,6 +22,10 @@
  *   mg_search_batch           the per-bucket Optimize.check() calls of the independence solver
  *                             (mythril/laser/smt/solver/independence_solver.py:119-140):
  *                             several different queries in one interpreter launch
+ *   mg_search_seeded / mg_eval_seeded
+ *                             the re-ask of a parent's constraint list plus one JUMPI condition
+ *                             (mythril/laser/ethereum/svm.py:252-257): candidates that start
+ *                             from the models of earlier queries instead of from nothing
  *   mg_eval / mg_eval_generated
  *                             ModelRef.eval(expr, model_completion=True)
  *                             (mythril/laser/smt/model.py:45-59) batched over
@@ -310,6 +314,45 @@ typedef struct mg_search_res {
   uint64_t first_hit, n_hits;
 } mg_search_res_t;
 int mg_search_batch(uint32_t n, const mg_search_req_t* reqs, uint32_t flags, mg_search_res_t* res);
+
+/* ---- seeded sweep: candidates that start from earlier models -------------- *
+ * A seed set is up to 32 earlier assignments, each with values for some of the program's
+ * coordinates.  Candidate i of a seeded sweep under (seed, generator):
+ *   g = i >> 6, lane = i & 63, m = g mod n_seeds, round = g / n_seeds   (m is per aligned group,
+ *   so wave-uniform, like every per-group choice of GEN3)
+ *   coordinate c is ELIGIBLE iff n_seeds > 0, coord_row[c] != MG_NONE, bit m of coord_has[c] is
+ *   set, and c is not a LAZY coordinate of the generator
+ *   replay lane (lane == 0 and round == 0): every eligible coordinate takes seed m's value, so
+ *   the first n_seeds groups each test one earlier model exactly
+ *   every other lane: an eligible coordinate takes seed m's value iff
+ *   (rnd(c, 0xFFFD) >> 16) < keep16, rnd being GEN3's with the candidate's lane key
+ *   (keep16 = 65536 keeps every eligible coordinate, 0 none)
+ *   every other coordinate has exactly the GEN3 value mg_search gives it for (seed, i, c); a
+ *   MIXED COPY copies the GENERATED final value of its source, seeded or not
+ *   seed values are masked to the coordinate's width
+ * The sweep runs the program's generator-independent lowering (the one mg_eval runs): seeded values
+ * lie outside the generator's domains, so a generator-specialised program's folded compares would
+ * be wrong for them.  It runs on the first device and is never split. */
+typedef struct mg_seed_set {
+  const uint32_t* rows;       /* n_rows x n_seeds words, SoA as mg_eval: limb row r of seed m at rows[r * n_seeds + m] */
+  const uint32_t* coord_row;  /* n_coords words: first row of coordinate c, MG_NONE = never seeded */
+  const uint32_t* coord_has;  /* n_coords words: bit m set = seed m has a value for coordinate c */
+  uint32_t n_seeds;           /* 0..32; 0 seeds nothing (the tables may then be null) */
+  uint32_t n_rows, keep16, reserved;
+} mg_seed_set_t;
+
+/* mg_search's conventions over the seeded candidates: first_hit exact in every mode, n_hits the
+ * window's count without MG_SEARCH_EARLY_EXIT, count = 0 gives {UINT64_MAX, 0}; assign_out
+ * (nullable): on a hit, the PROGRAM's watch rows (mg_program_info watch_words) of the winning
+ * candidate, from a one-candidate seeded pass; untouched on a miss.  Everything is checked before
+ * anything is queued: a bad handle, a null set, n_seeds > 32, keep16 > 65536, null tables with
+ * n_seeds > 0, or a coord_row[c] whose limbs run past n_rows give MG_E_INVALID and no launch. */
+int mg_search_seeded(uint64_t prog, uint64_t gen, const mg_seed_set_t* seeds, uint64_t seed, uint64_t start,
+                     uint64_t count, uint32_t flags, uint64_t* first_hit, uint64_t* n_hits, uint32_t* assign_out);
+/* mg_eval_generated over the seeded candidates [start, start + n): verdicts and (nullable) the
+ * program's watch rows, watch_words rows of n */
+int mg_eval_seeded(uint64_t prog, uint64_t gen, const mg_seed_set_t* seeds, uint64_t seed, uint64_t start,
+                   uint64_t n, uint8_t* verdict_out, uint32_t* watch_out);
 
 /* ---- JIT specialisation (comgr; hipRTC fallback) -----------------------
  * The compiler runs in a helper process (mythgpu_jitd, next to the library; started on the

@@ -103,7 +103,9 @@ static uint32_t lds_words_max() {
 __device__ __constant__ static const uint32_t kEmptyKeccak[8] = {
     0x5d85a470u, 0x7bfad804u, 0xca82273bu, 0xe500b653u, 0xdcc703c0u, 0x927e7db2u, 0x86f7233cu, 0xc5d24601u};
 
-enum Mode : int { MODE_EVAL = 0, MODE_GEN = 1, MODE_SEARCH = 2 };
+// MODE_SEEDED (k_run_seeded): GEN3 candidates with coordinates overridden from a seed set
+// (include/mythgpu.h, "seeded sweep"); SEARCH's reduction plus, when asked, GEN's per-candidate rows
+enum Mode : int { MODE_EVAL = 0, MODE_GEN = 1, MODE_SEARCH = 2, MODE_SEEDED = 3 };
 
 // Program data (instructions, literals, generator specs) is read-only for a kernel's
 // lifetime.  Reading it through the constant address space lets the compiler use
@@ -389,6 +391,42 @@ __device__ __forceinline__ void gen_coord(const KArgs& k, const VF& vf, uint32_t
   }
 }
 
+// The seed set of a seeded sweep (mg_seed_set_t on the device).  A kernel argument of its own, not
+// part of KArgs: every other kernel takes KArgs by value and k_run_batch copies it field by field.
+struct SeedArgs {
+  const uint32_t* rows;       // [n_rows][n_seeds]
+  const uint32_t* coord_row;  // [n_coords]
+  const uint32_t* coord_has;  // [n_coords]
+  uint32_t n_seeds, keep16;
+};
+
+// what one aligned group of a seeded sweep takes from the set: seed m, and whether lane 0 replays it
+struct SeedGroup {
+  SeedArgs s;
+  uint32_t m;
+  bool replay;  // round == 0: lane 0 takes every eligible coordinate
+};
+
+// After gen_coord wrote coordinate c's GEN3 value to dst: the seeded rule.  Everything that decides
+// eligibility is wave-uniform (kernel arguments, the group's seed number, tables read through the
+// constant address space), so it is a scalar branch, the seed's limbs are scalar loads at
+// rows[(row + j) * n_seeds + m], and keep-or-generate is one per-lane select per limb.
+template <class VF>
+__device__ __forceinline__ void seed_coord(const KArgs& k, const VF& vf, uint32_t dst, uint32_t c, uint32_t width,
+                                           const GKeys& ky, const SeedGroup& sg) {
+  if (sg.s.n_seeds == 0) return;
+  const uint32_t row = cst(sg.s.coord_row)[c];
+  if (row == MG_NONE || !((cst(sg.s.coord_has)[c] >> sg.m) & 1u)) return;
+  if (MG_GEN_KIND(cst((const uint32_t*)k.specs)[8u * c]) == MG_GEN_LAZY) return;
+  const bool keep = (sg.replay && (threadIdx.x & 63u) == 0u) || (grnd(ky, c, 0xFFFDu) >> 16) < sg.s.keep16;
+  const uint32_t L = (width + 31) >> 5;
+  const auto* r = cst(sg.s.rows) + (uint64_t)row * sg.s.n_seeds + sg.m;
+  for (uint32_t j = 0; j < L; j++) {
+    const uint32_t sv = r[(uint64_t)j * sg.s.n_seeds] & (j == L - 1 ? top_mask(width) : 0xFFFFFFFFu);
+    vf.at(dst + j) = keep ? sv : vf.at(dst + j);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // value-file helpers
 // ---------------------------------------------------------------------------
@@ -528,7 +566,8 @@ struct VFG {
 
 template <class VF, int MODE, int TIER, int KG>
 __device__ __forceinline__ void run_program(const KArgs& k, const VF& vf0, const uint64_t* i, const GKeys* key,
-                                            bool early, const bool* active, uint32_t* verdict, uint32_t vb) {
+                                            bool early, const bool* active, uint32_t* verdict, uint32_t vb,
+                                            const SeedGroup* sg = nullptr) {
 _Pragma("unroll")
   for (int g = 0; g < KG; g++) verdict[g] = 1;
   const uint32_t n_instr = k.n_instr;
@@ -551,6 +590,13 @@ _Pragma("unroll")
       case K_COORD: {
         if (MODE == MODE_EVAL) {
           MG_FOR_G(MG_LIMBS(L, vf.at(in.dst + j) = k.soa[(uint64_t)(in.p1 + j) * k.count + i[g]];););
+        } else if constexpr (MODE == MODE_SEEDED) {
+          // the GEN3 value (COPY chains included: a copy is of the source's generated value), then
+          // the group's seed over it
+          MG_FOR_G({
+            gen_coord<VFG<VF, KG>>(k, vf, in.dst, in.p0, W, key[g]);
+            seed_coord<VFG<VF, KG>>(k, vf, in.dst, in.p0, W, key[g], sg[g]);
+          });
         } else {
           MG_FOR_G(gen_coord<VFG<VF, KG>>(k, vf, in.dst, in.p0, W, key[g]););
         }
@@ -885,6 +931,22 @@ __global__ void __launch_bounds__(kWave) k_run(KArgs k) {
 #undef MG_VGRID
 }
 
+// A seeded sweep (mg_search_seeded / mg_eval_seeded): the same block body in MODE_SEEDED, one group
+// per wave per pass.  It runs the generator-INDEPENDENT lowering of the program (the one mg_eval
+// runs), never a generator's spec / spec_watch: those fold compares the generator's domains decide,
+// and a seeded value lies outside those domains.
+template <class VF, int TIER>
+__global__ void __launch_bounds__(kWave) k_run_seeded(KArgs k, SeedArgs sd) {
+  constexpr int MODE = MODE_SEEDED, KG = 1;
+#define MG_SEEDED 1
+#define MG_VB blockIdx.x
+#define MG_VGRID gridDim.x
+#include "run_body.inc"
+#undef MG_VB
+#undef MG_VGRID
+#undef MG_SEEDED
+}
+
 // One entry of a batched search launch (mg_search_batch): the arguments of one query's SEARCH
 // launch and the run of physical blocks [block0, block0 + nblocks) that sweeps it.  Entries are in
 // block order and cover the grid without gaps.
@@ -1202,6 +1264,10 @@ struct Engine {
   uint32_t* d_bstage = nullptr;
   uint32_t* h_bstage = nullptr;
   size_t bstage_words = 0;
+  // mg_search_seeded / mg_eval_seeded: the seed set of the call in flight (device, pinned image)
+  uint32_t* d_seed = nullptr;
+  uint32_t* h_seed = nullptr;
+  size_t seed_words = 0;
   mg_stats_t stats{};
   uint64_t refused_base = 0;  // jit_refused_total() at the last mg_stats_reset
 };
@@ -1983,6 +2049,10 @@ static void free_dev_buffers(Engine& e) {
   e.d_btab = e.h_btab = nullptr;
   e.d_bstage = e.h_bstage = nullptr;
   e.bstage_words = 0;
+  if (e.d_seed) (void)hipFree(e.d_seed);
+  if (e.h_seed) (void)hipHostFree(e.h_seed);
+  e.d_seed = e.h_seed = nullptr;
+  e.seed_words = 0;
   for (int q = 0; q < 4; q++) {
     if (e.xs[q]) (void)hipStreamDestroy(e.xs[q]);
     if (e.xev[q]) (void)hipEventDestroy(e.xev[q]);
@@ -2351,6 +2421,26 @@ int mg_eval_generated(uint64_t prog, uint64_t gen, uint64_t seed, uint64_t start
   return rc;
 }
 
+// one candidate's read-back buffers: ww watch rows on the device and pinned, and its verdict byte
+static int ensure_watch1(Engine& e, uint32_t ww) {
+  if (ww > e.watch1_words) {
+    if (e.d_watch1) (void)hipFree(e.d_watch1);
+    e.d_watch1 = nullptr;
+    e.watch1_words = 0;
+    HIPCHK(hipMalloc((void**)&e.d_watch1, (size_t)ww * 4));
+    e.watch1_words = ww;
+  }
+  if (ww > e.h_watch1_words) {
+    if (e.h_watch1) (void)hipHostFree(e.h_watch1);
+    e.h_watch1 = nullptr;
+    e.h_watch1_words = 0;
+    HIPCHK(hipHostMalloc((void**)&e.h_watch1, (size_t)ww * 4, hipHostMallocDefault));
+    e.h_watch1_words = ww;
+  }
+  if (!e.d_ver1) HIPCHK(hipMalloc((void**)&e.d_ver1, 64));
+  return MG_OK;
+}
+
 // the model of candidate `idx`: the watch rows of the generator's watch-list variant
 // (one interpreter lane; ~tens of microseconds) -> assign_out[watch_words]
 static int read_assignment(Engine& e, DevGen& g, uint64_t seed, uint64_t idx, uint32_t* assign_out) {
@@ -2374,14 +2464,8 @@ static int read_assignment(Engine& e, DevGen& g, uint64_t seed, uint64_t idx, ui
     if (rc) return rc;
   }
   if (g.spec_model.low.watch_words != ww) return set_err(MG_E_INVALID, "internal: model read-back layout");
-  if (ww > e.watch1_words) {
-    if (e.d_watch1) (void)hipFree(e.d_watch1);
-    e.d_watch1 = nullptr;
-    e.watch1_words = 0;
-    HIPCHK(hipMalloc((void**)&e.d_watch1, (size_t)ww * 4));
-    e.watch1_words = ww;
-  }
-  if (!e.d_ver1) HIPCHK(hipMalloc((void**)&e.d_ver1, 64));
+  int rc = ensure_watch1(e, ww);
+  if (rc) return rc;
   KArgs k{};
   k.specs = g.d_specs;
   k.gconsts = g.d_consts;
@@ -2390,14 +2474,7 @@ static int read_assignment(Engine& e, DevGen& g, uint64_t seed, uint64_t idx, ui
   k.watch = e.d_watch1;
   k.start = idx;
   k.seed = seed;
-  if (ww > e.h_watch1_words) {
-    if (e.h_watch1) (void)hipHostFree(e.h_watch1);
-    e.h_watch1 = nullptr;
-    e.h_watch1_words = 0;
-    HIPCHK(hipHostMalloc((void**)&e.h_watch1, (size_t)ww * 4, hipHostMallocDefault));
-    e.h_watch1_words = ww;
-  }
-  int rc = launch_async<MODE_GEN>(e, g.spec_model, k, 1);
+  rc = launch_async<MODE_GEN>(e, g.spec_model, k, 1);
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(e.h_watch1, e.d_watch1, (size_t)ww * 4, hipMemcpyDeviceToHost, e.stream));
   HIPCHK(hipEventRecord(e.ev2, e.stream));
@@ -2543,6 +2620,196 @@ int mg_search(uint64_t prog, uint64_t gen, uint64_t seed, uint64_t start, uint64
   std::lock_guard<std::mutex> g(e.mu);
   OnDevice od_(e);
   return search_locked(e, prog, gen, seed, start, count, flags, first_hit, n_hits, assign_out);
+}
+
+// ---- seeded sweeps (mg_search_seeded / mg_eval_seeded) ----------------------------------------
+
+// Everything a seeded call checks before anything is queued: the handles, the set's bounds, and
+// that every seeded coordinate's limbs lie inside the set's rows.
+static int check_seeded(Engine& e, uint64_t prog, uint64_t gen, const mg_seed_set_t* s, DevProgram** p_out,
+                        DevGen** g_out) {
+  if (!e.init) return set_err(MG_E_NOTINIT, "mg_init not called");
+  DevProgram* p = find_prog(e, prog);
+  if (!p) return set_err(MG_E_INVALID, "bad program handle");
+  auto it = e.gens.find(gen);
+  if (it == e.gens.end() || it->second->prog != prog) return set_err(MG_E_INVALID, "bad generator handle");
+  if (!s) return set_err(MG_E_INVALID, "seed set: null");
+  if (s->n_seeds > 32u) return set_err(MG_E_INVALID, "seed set: more than 32 seeds");
+  if (s->keep16 > 65536u) return set_err(MG_E_INVALID, "seed set: keep16 above 65536");
+  if (s->n_seeds) {
+    if (!s->rows || !s->coord_row || !s->coord_has) return set_err(MG_E_INVALID, "seed set: null table");
+    for (uint32_t c = 0; c < p->low.n_coords; c++) {
+      const uint32_t r = s->coord_row[c];
+      if (r == MG_NONE) continue;
+      const uint32_t L = (p->low.coord_width[c] + 31u) / 32u;
+      if ((uint64_t)r + L > s->n_rows) return set_err(MG_E_INVALID, "seed set: coordinate rows past n_rows");
+    }
+  }
+  *p_out = p;
+  *g_out = it->second.get();
+  return MG_OK;
+}
+
+// the set on the device: rows | coord_row | coord_has in one buffer, staged through pinned memory
+// and copied on the engine stream ahead of the launch that reads it
+static int stage_seeds(Engine& e, const DevProgram& p, const mg_seed_set_t* s, SeedArgs* sd) {
+  *sd = SeedArgs{nullptr, nullptr, nullptr, s->n_seeds, s->keep16};
+  if (!s->n_seeds) return MG_OK;
+  const size_t n_rows = (size_t)s->n_rows * s->n_seeds, nc = p.low.n_coords;
+  const size_t words = n_rows + 2 * nc;
+  if (words > e.seed_words) {
+    if (e.d_seed) (void)hipFree(e.d_seed);
+    if (e.h_seed) (void)hipHostFree(e.h_seed);
+    e.d_seed = e.h_seed = nullptr;
+    e.seed_words = 0;
+    size_t cap = 4096;
+    while (cap < words) cap <<= 1;
+    HIPCHK(hipMalloc((void**)&e.d_seed, cap * 4));
+    HIPCHK(hipHostMalloc((void**)&e.h_seed, cap * 4, hipHostMallocDefault));
+    e.seed_words = cap;
+  }
+  std::memcpy(e.h_seed, s->rows, n_rows * 4);
+  std::memcpy(e.h_seed + n_rows, s->coord_row, nc * 4);
+  std::memcpy(e.h_seed + n_rows + nc, s->coord_has, nc * 4);
+  HIPCHK(hipMemcpyAsync(e.d_seed, e.h_seed, words * 4, hipMemcpyHostToDevice, e.stream));
+  sd->rows = e.d_seed;
+  sd->coord_row = e.d_seed + n_rows;
+  sd->coord_has = e.d_seed + n_rows + nc;
+  return MG_OK;
+}
+
+// enqueue one k_run_seeded launch of program p (the generator-independent lowering) on e's stream,
+// bracketed by e.ev0 / e.ev1 like launch_async; primary device only, never split
+static int launch_seeded_async(Engine& e, DevProgram& p, const DevGen& g, KArgs k, const SeedArgs& sd, uint64_t count) {
+  if (!p.uploaded) {
+    int rc = upload_code(e, p);
+    if (rc) return rc;
+  }
+  const uint64_t lanes = (k.start + count) - (k.start & ~63ull);
+  // the value file's place and the grid: launch_async's rules at one group per wave
+  const bool lds = p.lds || (p.low.value_words <= 255u && lanes <= (uint64_t)std::max(e.cu_count, 1) * 2u * kWave);
+  const uint32_t grid = grid_for(e, lanes, lds, p.low.value_words, p.tier);
+  k.specs = g.d_specs;
+  k.gconsts = g.d_consts;
+  k.n_gconsts = (uint32_t)g.consts.size();
+  k.lds_g = kNoLds;
+  k.first_hit = e.d_hit;
+  k.hits = e.d_hit + 1;
+  k.sk = seed_lane_key(k.seed);
+  k.sg = seed_group_key(k.seed);
+  k.code = p.d_code;
+  k.consts = p.d_consts;
+  k.aux = p.d_aux;
+  k.coord_width = p.d_coord_width;
+  k.count = count;
+  k.n_instr = (uint32_t)p.low.code.size();
+  k.value_words = p.low.value_words;
+  k.n_specs = p.low.n_coords;
+  k.pc0 = p.low.n_hoisted;
+  k.flags |= kFlagPrefetch;
+  k.stride = (uint64_t)grid * kWave;
+  if (!lds) {
+    int rc = ensure_scratch(e, (size_t)p.low.value_words * k.stride * 4);
+    if (rc) return rc;
+    k.scratch = e.d_scratch;
+  }
+  const size_t shmem = lds ? (size_t)p.low.value_words * kWave * 4 : 0;
+  HIPCHK(hipEventRecord(e.ev0, e.stream));
+  const dim3 gr(grid), b(kWave);
+#define MG_RUN_SEEDED(VFT, TIERC) hipLaunchKernelGGL((k_run_seeded<VFT, TIERC>), gr, b, shmem, e.stream, k, sd)
+  if (lds) {
+    if (p.tier == kTierHeavy) MG_RUN_SEEDED(VFLds, kTierHeavy);
+    else if (p.tier == kTierMid) MG_RUN_SEEDED(VFLds, kTierMid);
+    else MG_RUN_SEEDED(VFLds, kTierLight);
+  } else {
+    if (p.tier == kTierHeavy) MG_RUN_SEEDED(VFGlobal, kTierHeavy);
+    else if (p.tier == kTierMid) MG_RUN_SEEDED(VFGlobal, kTierMid);
+    else MG_RUN_SEEDED(VFGlobal, kTierLight);
+  }
+#undef MG_RUN_SEEDED
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(e.ev1, e.stream));
+  return MG_OK;
+}
+
+int mg_search_seeded(uint64_t prog, uint64_t gen, const mg_seed_set_t* seeds, uint64_t seed, uint64_t start,
+                     uint64_t count, uint32_t flags, uint64_t* first_hit, uint64_t* n_hits, uint32_t* assign_out) {
+  Engine& e = E();
+  std::lock_guard<std::mutex> g(e.mu);
+  OnDevice od_(e);
+  DevProgram* p;
+  DevGen* dg;
+  int rc = check_seeded(e, prog, gen, seeds, &p, &dg);
+  if (rc) return rc;
+  unsigned long long res[2] = {~0ull, 0ull};
+  SeedArgs sd{};
+  if (count) {
+    if ((rc = stage_seeds(e, *p, seeds, &sd))) return rc;
+    KArgs k{};
+    k.start = start;
+    k.seed = seed;
+    k.flags = flags & MG_SEARCH_EARLY_EXIT;
+    if ((rc = arm_hits(e))) return rc;
+    if ((rc = launch_seeded_async(e, *p, *dg, k, sd, count))) return rc;
+    if ((rc = fetch_hits(e))) return rc;
+    if ((rc = collect_hits(e, e.stats, count, res))) return rc;
+  }
+  if (first_hit) *first_hit = res[0];
+  if (n_hits) *n_hits = res[1];
+  e.stats.hits += res[1];
+  const uint32_t ww = p->low.watch_words;
+  if (!assign_out || res[0] == ~0ull || ww == 0) return MG_OK;
+  // the winner's model: its watch rows from a one-candidate seeded pass of the same program
+  if ((rc = ensure_watch1(e, ww))) return rc;
+  KArgs k{};
+  k.start = res[0];
+  k.seed = seed;
+  k.verdict = e.d_ver1;
+  k.watch = e.d_watch1;
+  if ((rc = launch_seeded_async(e, *p, *dg, k, sd, 1))) return rc;
+  HIPCHK(hipMemcpyAsync(e.h_watch1, e.d_watch1, (size_t)ww * 4, hipMemcpyDeviceToHost, e.stream));
+  HIPCHK(hipEventRecord(e.ev2, e.stream));
+  HIPCHK(hipEventSynchronize(e.ev2));
+  std::memcpy(assign_out, e.h_watch1, (size_t)ww * 4);
+  return MG_OK;
+}
+
+int mg_eval_seeded(uint64_t prog, uint64_t gen, const mg_seed_set_t* seeds, uint64_t seed, uint64_t start, uint64_t n,
+                   uint8_t* verdict_out, uint32_t* watch_out) {
+  Engine& e = E();
+  std::lock_guard<std::mutex> g(e.mu);
+  OnDevice od_(e);
+  DevProgram* p;
+  DevGen* dg;
+  int rc = check_seeded(e, prog, gen, seeds, &p, &dg);
+  if (rc) return rc;
+  if (n && !verdict_out) return set_err(MG_E_INVALID, "verdict_out: null");
+  if (n == 0) return MG_OK;
+  const size_t watch_bytes = (size_t)p->low.watch_words * n * 4;
+  uint32_t* d_watch = nullptr;
+  uint8_t* d_ver = nullptr;
+  HIPCHK(hipMalloc((void**)&d_ver, n));
+  if (watch_out && watch_bytes && hipMalloc((void**)&d_watch, watch_bytes) != hipSuccess) {
+    (void)hipFree(d_ver);
+    return set_err(MG_E_NOMEM, "watch rows");
+  }
+  SeedArgs sd{};
+  KArgs k{};
+  k.start = start;
+  k.seed = seed;
+  k.verdict = d_ver;
+  k.watch = d_watch;
+  rc = stage_seeds(e, *p, seeds, &sd);
+  if (!rc) rc = arm_hits(e);
+  if (!rc) rc = launch_seeded_async(e, *p, *dg, k, sd, n);
+  if (!rc) rc = launch_wait(e, e.stats, n);
+  if (rc == MG_OK) {
+    HIPCHK(hipMemcpy(verdict_out, d_ver, n, hipMemcpyDeviceToHost));
+    if (d_watch) HIPCHK(hipMemcpy(watch_out, d_watch, watch_bytes, hipMemcpyDeviceToHost));
+  }
+  (void)hipFree(d_ver);
+  if (d_watch) (void)hipFree(d_watch);
+  return rc;
 }
 
 // an entry mg_search_batch can put into a k_run_batch launch: a latency-bound window (at most two

@@ -1,6 +1,7 @@
   // The body of an interpreter block (engine.hip: k_run, k_run_batch).  The including kernel
   // provides KArgs k, the names VF, MODE, TIER and KG, and the macros MG_VB (the block's id within
-  // its launch) and MG_VGRID (that launch's grid size).
+  // its launch) and MG_VGRID (that launch's grid size).  k_run_seeded also defines MG_SEEDED and
+  // provides SeedArgs sd (MODE_SEEDED, KG = 1).
   VF vf0(mg_lds, k, MG_VB);
   // the generator constants into LDS behind the value file (one wave per block: its own later
   // reads see the writes, LDS runs a wave's operations in order)
@@ -13,7 +14,7 @@
   const uint64_t total = (MODE == MODE_EVAL) ? k.count : (end - a0);
   // KG groups per wave per pass (run_program): a wave's pass covers KG * 64 consecutive indices
   const uint64_t step = (uint64_t)MG_VGRID * kWave * KG;
-  const bool early = (MODE == MODE_SEARCH) && (k.flags & MG_SEARCH_EARLY_EXIT);
+  const bool early = (MODE == MODE_SEARCH || MODE == MODE_SEEDED) && (k.flags & MG_SEARCH_EARLY_EXIT);
   uint64_t wave_best = ~0ull, wave_hits = 0;  // wave-uniform; published once per wave
   // idx & 63 == threadIdx.x & 63 below (a0 and base are multiples of 64): the lane half of
   // the GEN3 lane key is fixed per thread
@@ -74,11 +75,26 @@
 #pragma unroll
     for (int g = 0; g < KG; g++) key[g] = MODE != MODE_EVAL ? gen_keys_lk(a0 + base + (uint64_t)g * kWave, lk, k.sg) : GKeys{};
     uint32_t v[KG];
+#ifdef MG_SEEDED
+    // group number n of the seeded index space: seed n mod n_seeds, round n / n_seeds (wave-uniform,
+    // like every per-group choice of GEN3); KG = 1
+    SeedGroup sgrp[1];
+    {
+      const uint64_t n = (a0 + base) >> 6;
+      const uint32_t ns = sd.n_seeds ? sd.n_seeds : 1u;
+      sgrp[0].s = sd;
+      sgrp[0].m = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(n % ns));
+      sgrp[0].replay = n < ns;
+    }
+    run_program<VF, MODE, TIER, KG>(k, vf0, i, key, early, active, v, MG_VB, sgrp);
+#else
     run_program<VF, MODE, TIER, KG>(k, vf0, i, key, early, active, v, MG_VB);
+#endif
 #pragma unroll
     for (int g = 0; g < KG; g++) {
       v[g] = active[g] ? v[g] : 0u;
-      if (MODE == MODE_SEARCH) {
+      if (MODE == MODE_SEEDED && k.verdict && active[g]) k.verdict[i[g]] = (uint8_t)v[g];
+      if (MODE == MODE_SEARCH || MODE == MODE_SEEDED) {
         const unsigned long long m = __ballot(v[g] != 0);
         if (m) {
           const uint64_t first = a0 + base + (uint64_t)g * kWave + (uint64_t)(__ffsll((long long)m) - 1);
@@ -97,7 +113,7 @@
       }
     }
   }
-  if (MODE == MODE_SEARCH && threadIdx.x == 0) {
+  if ((MODE == MODE_SEARCH || MODE == MODE_SEEDED) && threadIdx.x == 0) {
     // a first hit that cannot lower the current minimum is not published; the count goes to the
     // block's stripe (kHitStripes)
     if (wave_best != ~0ull &&

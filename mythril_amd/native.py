@@ -51,7 +51,7 @@ EXPORTS = [
     "mg_init", "mg_collective_kind", "mg_shutdown", "mg_last_error", "mg_version", "mg_program_check", "mg_program_check_gen",
     "mg_program_specialized", "mg_program_load",
     "mg_program_info", "mg_program_free", "mg_gen_load", "mg_gen_info", "mg_gen_free", "mg_eval", "mg_eval_dev",
-    "mg_eval_generated", "mg_search", "mg_search_batch", "mg_keccak256", "mg_stats", "mg_stats_reset", "mg_dev_alloc",
+    "mg_eval_generated", "mg_search", "mg_search_batch", "mg_search_seeded", "mg_eval_seeded", "mg_keccak256", "mg_stats", "mg_stats_reset", "mg_dev_alloc",
     "mg_dev_free", "mg_dev_upload", "mg_dev_download", "mg_program_jit_source", "mg_program_jit_asm", "mg_code_object_check", "mg_jit_compile", "mg_jit_compile_ex", "mg_jit_verdicts", "mg_jit_info", "mg_jit_layout",
     "mg_jit_compile_async", "mg_jit_poll", "mg_jit_cancel", "mg_jit_helper_pid", "mg_cache_clear", "mg_split_range",
     "mg_jit_free", "mg_jit_search", "mg_jit_search_many", "mg_jit_eval", "mg_jit_eval_dev",
@@ -95,6 +95,38 @@ class SearchReq(C.Structure):
 
 class SearchRes(C.Structure):
     _fields_ = [("first_hit", C.c_uint64), ("n_hits", C.c_uint64)]
+
+
+class SeedSetC(C.Structure):
+    _fields_ = [
+        ("rows", C.POINTER(C.c_uint32)), ("coord_row", C.POINTER(C.c_uint32)), ("coord_has", C.POINTER(C.c_uint32)),
+        ("n_seeds", C.c_uint32), ("n_rows", C.c_uint32), ("keep16", C.c_uint32), ("reserved", C.c_uint32),
+    ]
+
+
+class SeedSet:
+    """``mg_seed_set_t``: up to 32 earlier assignments a seeded sweep starts from.  ``rows`` is the
+    [n_rows][n_seeds] uint32 SoA of their limbs, ``coord_row[c]`` the first row of coordinate c
+    (``MG_NONE``: never seeded), bit m of ``coord_has[c]`` says seed m has a value for c.  ``n_seeds``
+    and ``n_rows`` default to the shape of ``rows``; every field is passed to the library as given
+    (it validates them)."""
+
+    def __init__(self, rows=None, coord_row=None, coord_has=None, keep16: int = 65536,
+                 n_seeds: Optional[int] = None, n_rows: Optional[int] = None):
+        as_u32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint32)
+        self.rows, self.coord_row, self.coord_has = as_u32(rows), as_u32(coord_row), as_u32(coord_has)
+        if self.rows is not None and self.rows.ndim != 2:
+            raise ValueError("SeedSet: rows must be [n_rows][n_seeds]")
+        self.n_rows = int(n_rows if n_rows is not None else (0 if self.rows is None else self.rows.shape[0]))
+        self.n_seeds = int(n_seeds if n_seeds is not None else (0 if self.rows is None else self.rows.shape[1]))
+        self.keep16 = int(keep16)
+
+    def as_c(self) -> SeedSetC:
+        p = lambda a: None if a is None or a.size == 0 else _ptr(a, C.c_uint32)
+        return SeedSetC(p(self.rows), p(self.coord_row), p(self.coord_has), self.n_seeds, self.n_rows, self.keep16, 0)
+
+
+MG_NONE = 0xFFFFFFFF
 
 
 _lib = None
@@ -143,6 +175,10 @@ def load_library(path: Optional[Path] = None) -> C.CDLL:
             "mg_search": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32,
                                     u64p, u64p, u32p]),
             "mg_search_batch": (C.c_int, [C.c_uint32, C.POINTER(SearchReq), C.c_uint32, C.POINTER(SearchRes)]),
+            "mg_search_seeded": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(SeedSetC), C.c_uint64, C.c_uint64,
+                                           C.c_uint64, C.c_uint32, u64p, u64p, u32p]),
+            "mg_eval_seeded": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(SeedSetC), C.c_uint64, C.c_uint64,
+                                         C.c_uint64, u8p, u32p]),
             "mg_keccak256": (C.c_int, [u8p, u32p, C.c_uint64, u8p]),
             "mg_stats": (C.c_int, [C.POINTER(Stats)]),
             "mg_stats_reset": (C.c_int, []),
@@ -420,6 +456,33 @@ class Engine:
         flags = MG_SEARCH_EARLY_EXIT if early_exit else 0
         _check(self.lib.mg_search_batch(n, arr, flags, res))
         return [(None if res[q].first_hit == NO_HIT else int(res[q].first_hit), int(res[q].n_hits)) for q in range(n)]
+
+    def search_seeded(self, prog: int, gen: int, seeds: SeedSet, seed: int, start: int, count: int,
+                      early_exit: bool = True, assign: Optional[np.ndarray] = None):
+        """:meth:`search` over the seeded candidates of ``seeds`` (``mg_search_seeded``): the sweep runs
+        the program's generator-independent lowering, and ``assign`` gets the PROGRAM's watch rows
+        (``info(prog).watch_words``) of the winner."""
+        fh, nh = C.c_uint64(), C.c_uint64()
+        flags = MG_SEARCH_EARLY_EXIT if early_exit else 0
+        if assign is not None and (assign.dtype != np.uint32 or not assign.flags["C_CONTIGUOUS"] or
+                                   assign.size < self.info(prog).watch_words):
+            raise ValueError("search_seeded: assign must be a contiguous uint32 array of watch_words")
+        ap = _ptr(assign, C.c_uint32) if assign is not None else None
+        sc = seeds.as_c()
+        _check(self.lib.mg_search_seeded(prog, gen, C.byref(sc), seed, start, count, flags, C.byref(fh),
+                                         C.byref(nh), ap))
+        return (None if fh.value == NO_HIT else fh.value), nh.value
+
+    def eval_seeded(self, prog: int, gen: int, seeds: SeedSet, seed: int, start: int, n: int, watch_words: int = 0):
+        """:meth:`eval_generated` over the seeded candidates [start, start + n) (``mg_eval_seeded``)."""
+        if watch_words and watch_words < self.info(prog).watch_words:
+            raise ValueError("eval_seeded: fewer watch rows than the program stores")
+        ver = np.zeros(n, dtype=np.uint8)
+        watch = np.zeros((max(watch_words, 1), n), dtype=np.uint32) if watch_words else None
+        sc = seeds.as_c()
+        _check(self.lib.mg_eval_seeded(prog, gen, C.byref(sc), seed, start, n, _ptr(ver, C.c_uint8),
+                                       _ptr(watch, C.c_uint32) if watch is not None else None))
+        return ver, watch
 
     # JIT-specialised kernels --------------------------------------
     def jit_compile(self, prog: int, gen: int = 0, gen_verdicts: bool = False, asm: bool = False,

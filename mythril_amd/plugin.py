@@ -83,6 +83,9 @@ class HookStats:
         self.negative_hits = 0    # repeats of a GPU-missed unsat/unknown tuple sent straight to z3
         self.z3_queued_ms = 0.0   # raced z3 checks' waits for a worker (interrupted checks lingering)
         self.z3_unknown_beside_interrupted = 0  # z3 unknowns while an interrupted check still ran
+        self.warm_tried = 0        # searches whose first launch was seeded (MYTHGPU_WARM=1)
+        self.warm_hits = 0         # ... answered by that launch
+        self.warm_replay_hits = 0  # ... by an earlier model replayed as it was
 
     def __repr__(self):
         return (f"mythgpu: {self.queries} queries, {self.gpu_models} GPU models, {self.fallbacks} to z3 "
@@ -417,6 +420,31 @@ def _full_timeout() -> float:
         return float("inf")
 
 
+_WARM = None  # the process-wide ModelCache of MYTHGPU_WARM=1
+
+
+def _warm_kw() -> dict:
+    """``{"warm": cache}`` for ``search_partitioned`` under ``MYTHGPU_WARM=1`` (default off: {} and
+    the call is what it was): searches start from the models of earlier queries
+    (``search.ModelCache``).  A model found that way is re-checked by z3 like any other."""
+    global _WARM
+    if os.environ.get("MYTHGPU_WARM", "0") != "1":
+        return {}
+    if _WARM is None:
+        from .search import ModelCache
+
+        _WARM = ModelCache()
+    return {"warm": _WARM}
+
+
+def _count_warm(res) -> None:
+    if "seeded_ms" in getattr(res, "timing", {}):
+        STATS.warm_tried += 1
+    if getattr(res, "seeded", False):
+        STATS.warm_hits += 1
+        STATS.warm_replay_hits += bool(res.replay)
+
+
 def _gpu_search(terms, budget_s, cancel):
     from .native import Engine
     from .search import search_partitioned
@@ -424,10 +452,11 @@ def _gpu_search(terms, budget_s, cancel):
     t0 = time.perf_counter()
     try:
         res = search_partitioned(Engine.get(), terms, timeout_s=budget_s, max_candidates=1 << 40,
-                                 cancel=cancel, max_launch_s=RACE_LAUNCH_S)
+                                 cancel=cancel, max_launch_s=RACE_LAUNCH_S, **_warm_kw())
     finally:
         STATS.gpu_time += time.perf_counter() - t0
     STATS.candidates += res.scanned
+    _count_warm(res)
     return res
 
 
@@ -466,8 +495,9 @@ def _try_gpu(constraints, enforce_execution_time):
         return None
     cs, total, budget = b
     terms = z3bridge.to_terms(cs)
-    res = search_partitioned(Engine.get(), terms, timeout_s=budget / 1000.0, max_candidates=1 << 40)
+    res = search_partitioned(Engine.get(), terms, timeout_s=budget / 1000.0, max_candidates=1 << 40, **_warm_kw())
     STATS.candidates += res.scanned
+    _count_warm(res)
     z3m = _confirm(cs, res, total - (time.perf_counter() - t0) * 1e3)
     return None if z3m is None else Model([z3m])
 

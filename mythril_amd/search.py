@@ -266,6 +266,8 @@ class SearchResult:
         self.engine = "interp"
         self.buckets = 1
         self.timing = {}
+        self.seeded = False  # answered by the seeded first launch (``search(warm=...)``)
+        self.replay = False  # ... by one of its replay lanes: an earlier model as it was
 
 
 def _const_node_value(P: ssa.Program, node: int) -> Optional[int]:
@@ -425,6 +427,115 @@ def model_from_assignment(P: ssa.Program, assign: np.ndarray):
     return decode_model(P, [fb(raw[a:b], "little") for a, b in _model_plan(P)])
 
 
+def _is_lazy(P: ssa.Program, c: ssa.Coord) -> bool:
+    """A site whose default the program supplies (``default_generator`` gives it a LAZY spec)."""
+    return (c.kind == ssa.COORD_UF_SITE and P.nodes[c.node][7] != NONE) or \
+        (c.kind == ssa.COORD_ARRAY_SITE and P.nodes[c.node][6] != NONE)
+
+
+def coord_key(c: ssa.Coord):
+    """A coordinate's name across programs: its term (terms are hash-consed, so the same symbol or
+    site has the same id in every query of the process), or the AUX word's name.  Positions are
+    not stable: a new root can merge two buckets of the independence solver."""
+    return ("aux", c.name) if c.kind == ssa.COORD_AUX else ("t", c.term.id)
+
+
+def coords_from_assignment(P: ssa.Program, assign: np.ndarray) -> Dict[int, int]:
+    """{coordinate index: value} from the model watch rows a search wrote for a hit
+    (``_model_layout``): scalars, the AUX words in use, and every site's base value.  Left out:
+    a site whose base value is a slice of an AUX word (the word is there) and LAZY sites."""
+    raw = np.ascontiguousarray(assign, dtype="<u4").tobytes()
+    vals = [int.from_bytes(raw[a:b], "little") for a, b in _model_plan(P)]
+    _, _, (scal, aux, sites) = _model_layout(P)
+    out = {c.index: vals[pos] for (pos, _), c in zip(scal, P.scalar_coords())}
+    out.update({ci: vals[pos] for ci, pos in aux.items()})
+    for c, (_, _, _, _, bpos, _) in zip(P.sites, sites):
+        if bpos is not None and not _is_lazy(P, c):
+            out[c.index] = vals[bpos]
+    return out
+
+
+class ModelCache:
+    """Solved queries a later search starts from: a least-recently-used map of at most 256 entries
+    (``CAPACITY``), each the frozenset of a query's root term ids and its model as
+    ``{coord_key: (width, value)}``.  LASER's successor queries append one condition to the
+    parent's list (``svm.py:252-257``), so the parent's model satisfies one of the two successors
+    as it is and is a few symbols away from the other.
+
+    ``lookup`` hands the best matches to the engine as a seed set (``mg_search_seeded``)."""
+
+    CAPACITY = 256
+    MAX_SEEDS = 4
+
+    def __init__(self, capacity: int = CAPACITY):
+        from collections import OrderedDict
+
+        self.capacity = capacity
+        self._entries: "OrderedDict[frozenset, dict]" = OrderedDict()  # most recent last
+        self._alive: Dict[frozenset, tuple] = {}  # the entries' root terms
+
+    def __len__(self) -> int:
+        return len(self._entries)
+
+    def store(self, P: ssa.Program, roots: Sequence[T.Term], coords: Dict[int, int]) -> None:
+        """Remember the model ``coords`` ({coordinate index of P: value}) of the query ``roots``."""
+        key = frozenset(t.id for t in roots)
+        self._entries.pop(key, None)
+        self._entries[key] = {coord_key(P.coords[ci]): (P.coords[ci].width, int(v)) for ci, v in coords.items()
+                              if not _is_lazy(P, P.coords[ci])}
+        # term ids are only stable while the terms live (the hash-consing table holds them weakly)
+        self._alive[key] = tuple(roots)
+        while len(self._entries) > self.capacity:
+            self._alive.pop(self._entries.popitem(last=False)[0], None)
+
+    def ranked(self, roots: Sequence[T.Term]) -> List[dict]:
+        """The models of up to ``MAX_SEEDS`` entries that share a root with ``roots``: most shared
+        roots first, then most recently stored or used."""
+        ids = frozenset(t.id for t in roots)
+        found = [(len(key & ids), age, key) for age, key in enumerate(self._entries) if key & ids]
+        found.sort(key=lambda x: (-x[0], -x[1]))
+        found = found[:self.MAX_SEEDS]
+        for _, _, key in reversed(found):  # used: the best match becomes the most recent
+            self._entries.move_to_end(key)
+        return [self._entries[key] for _, _, key in found]
+
+    def lookup(self, P: ssa.Program, roots: Sequence[T.Term]):
+        """The seed set (``native.SeedSet``: rows, coord_row, coord_has) of ``ranked(roots)`` laid
+        out for P, matched by ``coord_key`` and width, or None when no entry shares a root or none
+        of their coordinates is one of P's.  ``keep16`` is left at 65536 (the caller chooses)."""
+        from .native import SeedSet
+
+        models = self.ranked(roots)
+        if not models:
+            return None
+        coord_row = np.full(len(P.coords), NONE, dtype=np.uint32)
+        coord_has = np.zeros(len(P.coords), dtype=np.uint32)
+        rows: List[List[int]] = []
+        for c in P.coords:
+            if _is_lazy(P, c):
+                continue
+            k = coord_key(c)
+            have = [m.get(k) for m in models]
+            have = [h if h is not None and h[0] == c.width else None for h in have]
+            if not any(h is not None for h in have):
+                continue
+            coord_row[c.index] = len(rows)
+            for j in range(ssa.limbs(c.width)):
+                rows.append([((h[1] >> (32 * j)) & 0xFFFFFFFF) if h is not None else 0 for h in have])
+            coord_has[c.index] = sum(1 << m for m, h in enumerate(have) if h is not None)
+        if not rows:
+            return None
+        return SeedSet(np.array(rows, dtype=np.uint32), coord_row, coord_has)
+
+
+def warm_keep16(n_eligible: int) -> int:
+    """``keep16`` of a seeded first launch: every eligible coordinate is redrawn from the generator
+    with probability p = min(1/2, 2 / n_eligible), so about two of them per lane once there are
+    four or more, and half of them below that; keep16 = 65536 - round(65536 p)."""
+    p = min(0.5, 2.0 / max(n_eligible, 1))
+    return P16 - int(round(P16 * p))
+
+
 # expected latency of one query-kernel compile (submit -> loadable module), seconds: an
 # exponential average of the compiles this process measured (cold value from the bench:
 # ~0.2 s on the MI355X box's host through hipRTC, less through comgr)
@@ -457,7 +568,8 @@ def _next_chunk(chunk: int, compiled: bool) -> int:
 def search(engine, roots: Sequence[T.Term], seed: int = 0x6D797468, chunk: int = 1 << 12,
            max_candidates: int = 1 << 26, timeout_s: float = 10.0, gen: Optional[GenBuilder] = None,
            want_model: bool = True, jit: str = "auto", jit_cost_s: Optional[float] = None,
-           cancel=None, max_launch_s: Optional[float] = None, start: int = 0) -> SearchResult:
+           cancel=None, max_launch_s: Optional[float] = None, start: int = 0,
+           warm: Optional[ModelCache] = None) -> SearchResult:
     """Find the lowest-index satisfying candidate (or give up: None).
 
     ``jit``: "never" keeps the generic interpreter (``k_run``, no compile latency);
@@ -478,7 +590,17 @@ def search(engine, roots: Sequence[T.Term], seed: int = 0x6D797468, chunk: int =
     ``start`` > 0 resumes the index stream there, as a search whose first launch of ``chunk``
     candidates covered ``[0, start)`` and missed (``search_many`` made that launch for several
     queries at once): ``start`` candidates count as scanned, the next launch has the size that
-    follows ``chunk`` and the JIT tiers are submitted as after a first miss."""
+    follows ``chunk`` and the JIT tiers are submitted as after a first miss.
+
+    ``warm``: a :class:`ModelCache`.  When it holds a model of a query that shares a root with
+    this one (and ``start`` is 0), the first launch is ONE seeded sweep (``mg_search_seeded``) of
+    ``[0, chunk)`` in the seeded index space: its first groups replay the cached models as they
+    are, the rest keep each seeded coordinate with probability ``warm_keep16`` and redraw the
+    others.  A hit there ends the search (``engine`` "seeded", ``seeded`` True, ``replay`` says
+    whether a replay lane won, ``timing["seeded_ms"]``); a miss continues exactly as without a
+    cache, from index 0 of the ordinary stream (the seeded candidates are not counted in
+    ``scanned``).  Every hit that returns a model is stored in the cache.  ``warm=None``: nothing
+    of this happens."""
     tp = time.perf_counter()
     P, blob = prepare(roots, gen)
     th = time.perf_counter()
@@ -489,6 +611,7 @@ def search(engine, roots: Sequence[T.Term], seed: int = 0x6D797468, chunk: int =
     hit = None
     hits = 0
     used = "interp"
+    seeded = replay = False
     expected_compile = JIT_COMPILE_S[0] if jit_cost_s is None else jit_cost_s
     expected_asm = JIT_ASM_COMPILE_S[0]
     assign = np.zeros(max(P.watch_words, 1), dtype=np.uint32) if want_model else None
@@ -514,7 +637,20 @@ def search(engine, roots: Sequence[T.Term], seed: int = 0x6D797468, chunk: int =
                     jit = "never"
             if start:
                 chunk = _next_chunk(chunk, jh is not None)
-            while scanned < max_candidates:
+            seeds = warm.lookup(P, roots) if warm is not None and start == 0 else None
+            if seeds is not None and not (cancel is not None and cancel.is_set()):
+                seeds.keep16 = warm_keep16(int((seeds.coord_row != NONE).sum()))
+                n = min(chunk, max_candidates)
+                ts = time.perf_counter()
+                idx, nh = engine.search_seeded(prog, gh, seeds, seed, 0, n, early_exit=True, assign=assign)
+                timing["seeded_ms"] = (time.perf_counter() - ts) * 1e3
+                timing["seeded_candidates"] = n
+                timing["seeds"] = seeds.n_seeds
+                if idx is not None:
+                    hit, hits, used, seeded = idx, nh, "seeded", True
+                    replay = idx & 63 == 0 and (idx >> 6) < seeds.n_seeds
+                    scanned = n
+            while scanned < max_candidates and not seeded:
                 now = time.perf_counter()
                 left = timeout_s - (now - t0)
                 if left <= 0 or (cancel is not None and cancel.is_set()):
@@ -639,6 +775,7 @@ def search(engine, roots: Sequence[T.Term], seed: int = 0x6D797468, chunk: int =
     dt = time.perf_counter() - t0
     res = SearchResult(hit, hits, scanned, dt)
     res.engine = used
+    res.seeded, res.replay = seeded, replay
     if tier is not None:
         timing["jit_tier"] = tier
     global LAST_ENGINE, LAST_RESULT
@@ -647,6 +784,8 @@ def search(engine, roots: Sequence[T.Term], seed: int = 0x6D797468, chunk: int =
         # the search only reports indices whose verdict is 1
         tm = time.perf_counter()
         res.model = (1,) + model_from_assignment(P, assign) + (P,)
+        if warm is not None:
+            warm.store(P, roots, coords_from_assignment(P, assign))
         timing["model_ms"] = (time.perf_counter() - tm) * 1e3
     timing["search_ms"] = dt * 1e3
     res.timing = timing
@@ -655,7 +794,8 @@ def search(engine, roots: Sequence[T.Term], seed: int = 0x6D797468, chunk: int =
 
 def search_many(engine, queries: Sequence[Sequence[T.Term]], seed: int = 0x6D797468, chunk: int = 1 << 12,
                 max_candidates: int = 1 << 26, timeout_s: float = 10.0, gen: Optional[GenBuilder] = None,
-                want_model: bool = True, cancel=None, stop_at_give_up: bool = False, **kw) -> List[SearchResult]:
+                want_model: bool = True, cancel=None, stop_at_give_up: bool = False, warm=None,
+                **kw) -> List[SearchResult]:
     """``search`` for several independent queries, their first launches as ONE engine call
     (``mg_search_batch``: one interpreter launch sweeps ``[0, chunk)`` of every query and captures
     the models of those that hit).  A query that hit there is finished; one that missed continues
@@ -664,7 +804,10 @@ def search_many(engine, queries: Sequence[Sequence[T.Term]], seed: int = 0x6D797
 
     Budgets and ``cancel`` are checked before the batch and before each continuation; a query that
     is not reached gets a result without an index.  ``stop_at_give_up``: after the first query that
-    gives up the remaining continuations are skipped (``search_partitioned`` needs every bucket)."""
+    gives up the remaining continuations are skipped (``search_partitioned`` needs every bucket).
+
+    ``warm`` is ignored: batched first launches are not seeded (``mg_search_batch`` has no seeded
+    entries), and the continuations resume the ordinary stream."""
     t0 = time.perf_counter()
 
     def gave_up(scanned=0):
@@ -726,7 +869,10 @@ def search_partitioned(engine, roots: Sequence[T.Term], timeout_s: float = 10.0,
 
     ``batch=True`` (or ``MYTHGPU_BATCH=1`` when ``batch`` is None) sends the buckets' first launches
     to the engine as one call (``search_many``) instead of one search after the other; the result is
-    the same either way.  Default: off."""
+    the same either way.  Default: off.
+
+    ``warm`` (a :class:`ModelCache`, see ``search``) goes to each bucket's search when the buckets
+    are searched one after the other; the batched path ignores it."""
     from .partition import partition
 
     buckets = partition(roots)
@@ -738,6 +884,7 @@ def search_partitioned(engine, roots: Sequence[T.Term], timeout_s: float = 10.0,
     idx, hits, scanned = [], 0, 0
     ver, scalars, arrays, funcs, progs = 1, {}, {}, {}, []
     engines = set()
+    parts: List[SearchResult] = []
     many = iter(search_many(engine, buckets, timeout_s=timeout_s, stop_at_give_up=True, **kw)) if batch else None
     for b in buckets:
         left = timeout_s - (time.perf_counter() - t0)
@@ -751,6 +898,7 @@ def search_partitioned(engine, roots: Sequence[T.Term], timeout_s: float = 10.0,
             r = search(engine, b, timeout_s=left, **kw)
         scanned += r.scanned
         engines.add(getattr(r, "engine", "interp"))
+        parts.append(r)
         if r.index is None:
             res = SearchResult(None, 0, scanned, time.perf_counter() - t0)
             res.buckets = len(buckets)
@@ -767,6 +915,11 @@ def search_partitioned(engine, roots: Sequence[T.Term], timeout_s: float = 10.0,
     res = SearchResult(tuple(idx), hits, scanned, time.perf_counter() - t0)
     res.buckets = len(buckets)
     res.engine = "+".join(sorted(engines))
+    # seeded first launches (``warm``): their time summed; seeded / replay when every bucket was
+    if any("seeded_ms" in r.timing for r in parts):
+        res.timing["seeded_ms"] = sum(r.timing.get("seeded_ms", 0.0) for r in parts)
+    res.seeded = all(r.seeded for r in parts)
+    res.replay = all(r.replay for r in parts)
     if kw.get("want_model", True):
         res.model = (ver, scalars, arrays, funcs, progs)
     return res
