@@ -1407,7 +1407,9 @@ static void fill_info(const DevProgram& p, mg_program_info_t* info) {
   info->n_coords = p.low.n_coords;
   info->n_roots = p.low.n_roots;
   info->value_words = p.low.value_words;
-  info->uses_lds = p.lds;
+  // upload_code (at the first launch) sets p.lds by this rule: a program asked before it has run
+  // gets the same answer as after, and as mg_program_check's
+  info->uses_lds = p.uploaded ? p.lds : p.low.value_words <= lds_words_max();
   info->n_watch = p.low.n_watch;
   info->watch_words = p.low.watch_words;
   info->coord_words = p.low.coord_words;

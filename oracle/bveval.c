@@ -22,7 +22,9 @@
 #include <omp.h>
 #endif
 
-#define MAXW 16 /* 64-bit words per value: 1024 bits */
+#ifndef MAXW
+#define MAXW 16 /* 64-bit words per value: 1024 bits (the wide test build: -DMAXW=64) */
+#endif
 #define NONE 0xFFFFFFFFu
 
 typedef struct { uint64_t w[MAXW]; } val_t;
@@ -207,7 +209,7 @@ static void vshl1(val_t* a) {
   a->w[0] <<= 1;
 }
 
-/* long division, bit by bit from the top (any width <= 1024) */
+/* long division, bit by bit from the top (any width <= 64 * MAXW) */
 static void vdivrem(const val_t* a, const val_t* b, uint32_t width, val_t* q, val_t* r) {
   vzero(q);
   vzero(r);

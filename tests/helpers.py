@@ -315,3 +315,179 @@ def random_tier_program(seed: int, n_ops: int = 36, full: bool = False):
         bools.append(rng.choice([T.and_(x, y), T.or_(x, y), T.not_(x), T.xor_(x, y), T.eq(x, y)]))
     # an OR of a few of them: satisfiable by many candidates, so verdicts carry information
     return [T.or_(*rng.sample(bools, min(3, len(bools)))), T.or_(*rng.sample(bools, min(3, len(bools))))]
+
+
+# ---------------------------------------------------------------------------
+# values above 1024 bits and multi-block Keccak (tests/test_wide_cpu.py, tests/test_gpu_wide.py,
+# the wide records of tests/test_asm_sim.py)
+# ---------------------------------------------------------------------------
+# Keccak input lengths in bytes: every partial-word remainder, the word and lane edges, the
+# block edge of the rate (135 / 136 / 137, 271 / 272 / 273, 408 = 3 x 136) and several blocks
+LENS = (1, 2, 3, 4, 5, 7, 8, 9, 20, 31, 32, 33, 55, 63, 64, 65, 100, 127, 128, 129, 134, 135, 136, 137, 200, 255,
+        256, 257, 271, 272, 273, 408, 500, 512)
+
+
+def lit_bytes(n: int, salt: int = 0) -> T.Term:
+    """An ``n``-byte literal with no zero and no repeated neighbouring bytes (a byte read from the
+    wrong place changes the digest)."""
+    data = bytes(((i * 37 + 11 * salt + 1) % 255) + 1 for i in range(n))
+    return T.BitVecVal(int.from_bytes(data, "big"), 8 * n)
+
+
+def memory_region_queries():
+    """SHA3 over a memory region as LASER builds it: a ``Concat`` of literal bytes and symbols of any
+    concrete length (``keccak_function_manager.py:59-72``).  {name: (roots, region bytes)}; each root
+    is ``ULT(keccak(region), 2^255) OR z == 7`` over the 256-bit symbols x, y and the 8-bit z."""
+    from oracle.keccak import keccak256_int
+
+    x, y, z = T.BitVecVar("mr_x", 256), T.BitVecVar("mr_y", 256), T.BitVecVar("mr_z", 8)
+    byte = lambda v, i: T.extract(8 * i + 7, 8 * i, v)  # noqa: E731
+    # fully constant: a literal whose digest is >= 2^255, so the verdict is z == 7 alone
+    salt = next(s for s in range(64) if keccak256_int(lit_bytes(200, s).params[0].to_bytes(200, "big")) >> 255)
+    regions = {
+        "literal_across_block_edge": T.concat(lit_bytes(4), x, lit_bytes(100, 1), y, lit_bytes(3, 2)),  # 171
+        "both_pad_bits_in_one_byte": T.concat(x, lit_bytes(103)),  # 135
+        "block0_all_literal": T.concat(lit_bytes(135), z),  # 136
+        "one_byte_into_block1": T.concat(z, lit_bytes(136)),  # 137
+        "interleaved_bytes": T.concat(byte(x, 0), lit_bytes(1, 3), byte(y, 31), lit_bytes(2, 4), x, lit_bytes(130, 5),
+                                      byte(y, 0), lit_bytes(1, 6), byte(x, 1)),  # 170
+        "fully_constant": lit_bytes(200, salt),
+    }
+    out = {}
+    for name, region in regions.items():
+        root = T.or_(T.bvcmp("bvult", T.keccak256(region), T.BitVecVal(1 << 255, 256)),
+                     T.eq(z, T.BitVecVal(7, 8)))
+        out[name] = ([root], region.width // 8)
+    assert [n for _, n in out.values()] == [171, 135, 136, 137, 170, 200]
+    return out
+
+
+def wide_edge_values(w: int, rng: random.Random, n_random: int = 6):
+    """Operand pairs (a, b) at width ``w`` > 1024: the extremes, 2^1024 and its predecessor (the C
+    port's old limit), pairs that differ only in limb 0 or only in the top limb, and
+    ``2^w - 1, 1`` (a carry through every limb)."""
+    m = (1 << w) - 1
+    top = 32 * ((w - 1) // 32)  # bit 0 of the top limb
+    r = rng.getrandbits(w)
+    singles = [0, 1, m, 1 << (w - 1), (1 << (w - 1)) - 1, 1 << 1024, (1 << 1024) - 1]
+    pairs = [(a, b) for a in singles for b in (0, 1, m, 1 << (w - 1), (1 << 1024) - 1)]
+    pairs += [(r, r ^ 1), (r ^ 1, r), (r, r ^ (1 << top)), (r ^ (1 << top), r), (r, r), (m, 1), (1, m),
+              (m - 1, 1), (1 << top, (1 << top) - 1)]
+    pairs += [(rng.getrandbits(w), rng.getrandbits(w)) for _ in range(n_random)]
+    return pairs
+
+
+def wide_operator_terms(w: int, a: T.Term = None, b: T.Term = None):
+    """Every operator the lowering admits above 256 bits, at width ``w`` over the variables a and b
+    (a Bool c for ITE): ADD / SUB / AND / OR / XOR / NOT / NEG, CONCAT / EXTRACT / ZEXT / SEXT, ITE,
+    EQ / ULT / ULE / SLT / SLE (and their mirrored forms).  Returns (a, b, c, [terms])."""
+    a = a or T.BitVecVar(f"wa{w}", w)
+    b = b or T.BitVecVar(f"wb{w}", w)
+    c = T.BoolVar(f"wc{w}")
+    terms = [T.bvbin(op, a, b) for op in ("bvadd", "bvsub", "bvand", "bvor", "bvxor")]
+    terms += [T.bvun("bvnot", a), T.bvun("bvneg", a), T.bvun("bvneg", b)]
+    terms += [T.bvcmp(op, a, b) for op in ("bvult", "bvule", "bvugt", "bvuge", "bvslt", "bvsle", "bvsgt", "bvsge")]
+    terms += [T.eq(a, b), T.ite(c, a, b)]
+    # extracts: 32 bits at the offsets where limbs split (0, 1, 31, 32, 33, W-33, around bit 1024),
+    # one bit, and slices that are themselves wider than 1024 bits
+    for lo in (0, 1, 31, 32, 33, w - 33, 1023, 1024):
+        hi = min(lo + 31, w - 1)
+        terms.append(T.extract(hi, lo, a))
+    terms += [T.extract(w - 1, w - 1, a), T.extract(1024, 1023, a), T.extract(w - 1, 1, a), T.extract(w - 2, 0, b),
+              T.extract(w - 1, 33, T.bvbin("bvadd", a, b))]
+    lo_half = T.extract(w // 2 - 1, 0, a)
+    hi_half = T.extract(w - 1, w // 2, b)
+    terms += [T.concat(hi_half, lo_half), T.eq(T.concat(T.extract(w - 1, w // 2, a), lo_half), a)]
+    if w + 64 <= 4096:
+        terms += [T.zero_extend(33, a), T.sign_extend(33, a), T.sign_extend(64, T.extract(w - 2, 0, b)),
+                  T.concat(a, T.BitVecVal(0xA5, 8)), T.concat(T.BitVecVal(0x5A, 8), b)]
+    terms += [T.zero_extend(w - 8, T.extract(7, 0, a)), T.sign_extend(w - 8, T.extract(7, 0, b)),
+              T.sign_extend(w - 1025, T.extract(1024, 0, a))]
+    return a, b, c, terms
+
+
+class WideRandomProgram:
+    """``RandomProgram`` above 1024 bits: a random DAG over variables of ``widths`` (two of each)
+    with the operators the lowering admits there, slices of any width, concatenations up to
+    ``max_width``, a UF and concrete Keccak over wide keys.  ``terms`` are compared value by value;
+    ``roots`` are two ORs of its Bools."""
+
+    def __init__(self, seed: int, n_ops: int = 40, widths=(1025, 1088, 2048, 4096), max_width: int = 4096):
+        rng = random.Random(seed)
+        pool: Dict[int, List[T.Term]] = {}
+
+        def add(t):
+            pool.setdefault(t.width, []).append(t)
+            return t
+
+        for w in widths:
+            add(T.BitVecVar(f"w{seed}_a{w}", w))
+            add(T.BitVecVar(f"w{seed}_b{w}", w))
+            add(T.BitVecVal(rng.choice([1, (1 << w) - 1, 1 << 1024, (1 << 1024) - 1, rng.getrandbits(w)]), w))
+        bools: List[T.Term] = [T.BoolVar(f"w{seed}_flag")]
+        fns = {w: T.FuncDecl(f"keccak256_{w}", w, 256) for w in widths}
+        terms: List[T.Term] = []
+        for _ in range(n_ops):
+            kind = rng.random()
+            w = rng.choice(widths)
+            a, b = rng.choice(pool[w]), rng.choice(pool[w])
+            if kind < 0.25:
+                t = T.bvbin(rng.choice(["bvadd", "bvsub", "bvand", "bvor", "bvxor"]), a, b)
+            elif kind < 0.35:
+                t = T.bvun(rng.choice(["bvnot", "bvneg"]), a)
+            elif kind < 0.55:
+                op = rng.choice(["eq", "bvult", "bvule", "bvugt", "bvuge", "bvslt", "bvsle", "bvsgt", "bvsge"])
+                c = T.eq(a, b) if op == "eq" else T.bvcmp(op, a, b)
+                bools.append(c)
+                terms.append(c)
+                continue
+            elif kind < 0.63:
+                t = T.ite(rng.choice(bools), a, b)
+            elif kind < 0.75:
+                lo = rng.choice([0, 1, 31, 32, 33, 1023, 1024, rng.randrange(w)])
+                lo = min(lo, w - 1)
+                hi = rng.choice([w - 1, min(w - 1, lo + 31), rng.randrange(lo, w)])
+                t = T.extract(hi, lo, a)
+            elif kind < 0.83:
+                other = rng.choice(pool[rng.choice(sorted(pool))])
+                t = T.concat(a, other) if a.width + other.width <= max_width else T.bvbin("bvxor", a, b)
+            elif kind < 0.90:
+                src_w = rng.choice([x for x in sorted(pool) if x <= w])
+                src = rng.choice(pool[src_w])
+                t = (T.zero_extend if rng.random() < 0.5 else T.sign_extend)(w - src_w, src)
+            elif kind < 0.95:
+                t = T.app(fns[w], a)
+            else:
+                t = T.keccak256(a) if w % 8 == 0 else T.app(fns[w], b)
+            add(t)
+            terms.append(t)
+            if rng.random() < 0.3:
+                c = T.eq(t, rng.choice(pool[t.width]))
+                bools.append(c)
+                terms.append(c)
+        self.terms = terms
+        self.bools = bools
+        self.roots = [T.or_(*rng.sample(bools, min(3, len(bools)))), T.or_(*rng.sample(bools, min(3, len(bools))))]
+
+
+def keccak_sweep_inputs(nbytes: int, rng: random.Random, n_random: int = 12):
+    """Inputs of a Keccak length sweep as integers (big-endian messages): zero, all ones, only the
+    first byte 0x01, only the last byte 0x80 (the pad bits' mirror images), and random values."""
+    w = 8 * nbytes
+    return [0, (1 << w) - 1, 1 << (w - 8), 0x80] + [rng.getrandbits(w) for _ in range(n_random)]
+
+
+def wide_literal_tail_query():
+    """``literal_tail_query`` above 1024 bits: keys ``Concat(key, literal)`` of 1088 bits (a 256-bit
+    symbol over an 832-bit literal tail, the shape of a hashed memory region with a symbolic head)
+    in an EQ of an ITE, in UF keys with equal and with different tails, and ORs so that verdicts
+    carry information."""
+    a, b, d, e = (T.BitVecVar(f"wk_{n}", 256) for n in "abde")
+    f = T.BoolVar("wk_f")
+    tail, other = lit_bytes(104, 7), lit_bytes(104, 8)
+    k1, k2, k3 = T.concat(a, tail), T.concat(b, tail), T.concat(d, tail)
+    h = T.FuncDecl("keccak256_1088", 1088, 256)
+    ult = lambda x, y: T.bvcmp("bvult", x, y)  # noqa: E731
+    return [T.or_(T.eq(T.ite(ult(a, b), k1, k2), k3), ult(d, a)),
+            T.or_(ult(T.app(h, k1), T.bvbin("bvadd", T.app(h, k3), T.BitVecVal(3, 256))), f),
+            T.or_(T.not_(T.eq(T.app(h, T.concat(e, other)), T.app(h, k2))), T.eq(k1, T.concat(e, other)), f)]

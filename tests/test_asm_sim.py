@@ -51,7 +51,10 @@ CONFIGS = [
 ]
 
 
-def _build(out: Path, sanitize: bool) -> Path:
+WIDE_MAXW = 64  # the C port's words per value in the wide driver (oracle/build_c.py: 4096 bits)
+
+
+def _build(out: Path, sanitize: bool, wide: bool = False) -> Path:
     from mythril_amd import build
 
     build.write_prelude()
@@ -74,6 +77,8 @@ def _build(out: Path, sanitize: bool) -> Path:
             "-I/opt/rocm/include", f"-I{ROOT}", "-c", str(ROOT / src), "-o", str(o)]
         if not sanitize:
             cmd.append("-DASMSIM_ASSEMBLER")
+        if wide and src == "oracle/bveval.c":
+            cmd.append(f"-DMAXW={WIDE_MAXW}")
         jobs.append(subprocess.Popen(cmd, stderr=subprocess.PIPE, text=True))
         objs.append(str(o))
     for j in jobs:
@@ -90,11 +95,11 @@ SOURCES = ["mythril_amd/csrc/program.cpp", "mythril_amd/csrc/program.hpp", "myth
            "tests/asmsim/asmsim.hpp", "oracle/bveval.c"]
 
 
-def _cached(tmp_path_factory, sanitize: bool) -> Path:
+def _cached(tmp_path_factory, sanitize: bool, wide: bool = False) -> Path:
     """A driver build, cached under /tmp by a hash of its sources (a rebuild costs ~40 s)."""
     import hashlib
 
-    h = hashlib.sha256()
+    h = hashlib.sha256(f"MAXW={WIDE_MAXW}".encode() if wide else b"")
     for s in SOURCES + (["mythril_amd/csrc/jit.cpp"] if not sanitize else []):
         h.update((ROOT / s).read_bytes())
     cache = Path("/tmp") / f"mythgpu-asmsim-{h.hexdigest()[:16]}"
@@ -102,7 +107,7 @@ def _cached(tmp_path_factory, sanitize: bool) -> Path:
     exe = cache / name
     if exe.exists():
         return exe
-    built = _build(tmp_path_factory.mktemp(name), sanitize=sanitize)
+    built = _build(tmp_path_factory.mktemp(name), sanitize=sanitize, wide=wide)
     cache.mkdir(parents=True, exist_ok=True)
     shutil.copy2(built, cache / (name + ".tmp"))
     os.replace(cache / (name + ".tmp"), exe)
@@ -113,6 +118,13 @@ def _cached(tmp_path_factory, sanitize: bool) -> Path:
 def sim(tmp_path_factory):
     """The differential driver (emitter, simulator and C port at -O2; comgr's assembler linked)."""
     return _cached(tmp_path_factory, sanitize=False)
+
+
+@pytest.fixture(scope="module")
+def sim_wide(tmp_path_factory):
+    """``sim`` with the C port at -DMAXW=64: it follows the kernels above 1024 bits (the default
+    driver reports such a program as an error of the reference, not as verdicts)."""
+    return _cached(tmp_path_factory, sanitize=False, wide=True)
 
 
 @pytest.fixture(scope="module")
@@ -468,7 +480,8 @@ def _full_worker(args):
 
 def test_asm_tier_full_vocabulary_sim(sim):
     """Round 5's vocabulary in the tier — symbolic UDIV/UREM, SDIV/SREM/SMOD, variable SHL/LSHR/ASHR,
-    EXP and Keccak-256 (one and several blocks) — per candidate equal to the C port on LASER-shaped
+    EXP and Keccak-256 (inputs of 32 and 64 bytes: one sponge block; longer inputs and a second
+    block: ``test_asm_tier_wide_values_sim``) — per candidate equal to the C port on LASER-shaped
     queries (``lasergen.laser_query(full=True)``) and random programs (search, gen and eval kernels)."""
     n_l = int(os.environ.get("MYTHGPU_SIMFUZZ_FULL_N", "1000"))
     n_t = n_l // 2
@@ -486,17 +499,116 @@ def test_asm_tier_full_vocabulary_sim(sim):
     assert total["ok"] >= 0.995 * (n_l + 2 * n_t), total
 
 
-def _mutants(tmp_path: Path, mutants) -> dict:
+def _eval_blob(P, watch_terms=()) -> bytes:
+    """The eval program of P with exactly ``watch_terms`` watched (their rows are compared too)."""
+    prev = P.watch
+    P.set_watch([P.term_node[t.id] for t in watch_terms])
+    pb = P.to_bytes()
+    P.set_watch(prev)
+    return pb
+
+
+def _wide_queries(max_keccak_len: int = 256, lens=None):
+    """[(name, roots, watched terms)] above 1024 bits inside the first tier (values up to 2048 bits):
+    Keccak over every length of ``LENS`` up to ``max_keccak_len`` bytes, the memory-region queries,
+    every wide operator at the limb edges, and random wide DAGs."""
+    from mythril_amd.smt import terms as T
+    from tests.helpers import LENS, WideRandomProgram, memory_region_queries, wide_operator_terms
+
+    half = T.BitVecVal(1 << 255, 256)
+    out = []
+    for n in (LENS if lens is None else lens):
+        if n <= max_keccak_len:
+            h = T.keccak256(T.BitVecVar(f"kx{n}", 8 * n))
+            out.append((f"keccak{n}", [T.bvcmp("bvult", h, half)], [h]))
+    if lens is not None:
+        return out
+    for name, (roots, _) in memory_region_queries().items():
+        digest = roots[0].args[0].args[0]
+        assert digest.op == "keccak256"
+        out.append((name, roots, [digest]))
+    for w in (1025, 1056, 1088, 2047, 2048):
+        a, b, c, terms = wide_operator_terms(w)
+        terms = [t for t in terms if all(s.sort[0] != "bv" or s.width <= 2048 for s in T.postorder([t]))]
+        bools = [t for t in terms if t.is_bool]
+        for k in range(0, len(terms), 4):  # a few watched values per kernel: 64 limbs each at 2048 bits
+            chunk = terms[k:k + 4]
+            low = [T.eq(T.extract(0, 0, t), T.BitVecVal(1, 1)) if t.is_bv else t for t in chunk]
+            out.append((f"ops{w}_{k}", [T.or_(*low[:2]), T.or_(*low[2:], bools[k % len(bools)])], chunk))
+    for seed in range(6):
+        rp = WideRandomProgram(900 + seed, n_ops=30, widths=(1025, 1088, 2048), max_width=2048)
+        out.append((f"dag{seed}", rp.roots, []))
+    return out
+
+
+def _wide_records(queries, assemble: bool = True):
+    """(records, their count): each query as a search record and as row-major and tiled eval records
+    (the watched terms' rows compared with the C port's); every fifth record also through comgr
+    (``assemble``: the mutant drivers are built without the assembler)."""
+    from mythril_amd import search
+
+    rng = random.Random(0x51DE)
+    recs = []
+    for name, roots, watch in queries:
+        P, blob = search.prepare(roots)
+        start = rng.getrandbits(63)
+        if len(recs) % 2:
+            start = (start & ~0xFFFFFFFF) | 0x80000000 | rng.getrandbits(31)
+        recs.append((0, P.to_bytes(), blob, start, 64 * 2 + 9))
+        pe = _eval_blob(P, watch)
+        recs.append((1, pe, None, 0, 64 + 7))
+        recs.append((2, pe, None, 0, 64 + 7))
+    return b"".join(record(kind, pb, blob, rng.getrandbits(32), start, count, flags=int(assemble and i % 5 == 0))
+                    for i, (kind, pb, blob, start, count) in enumerate(recs)), len(recs)
+
+
+def _wide_worker(args):
+    exe, lo, hi = args
+    recs, n = _wide_records(_wide_queries()[lo:hi])
+    rc, summary, bad, err = run_sim(Path(exe), recs, {"MYTHGPU_JIT_ASM_CHECK": "1"})
+    return rc, summary, bad[:5], err[-3000:], n
+
+
+def test_asm_tier_wide_values_sim(sim_wide):
+    """The first tier above 1024 bits against the wide C port (``sim_wide``): Keccak-256 over every
+    length of ``helpers.LENS`` up to 256 bytes (every partial-word remainder of ``word_at``, 135 /
+    136 / 137 bytes, the second sponge block), the memory-region queries (literals and symbols mixed,
+    a literal across the block edge, an all-literal block 0), every operator admitted above 256
+    bits at 1025 .. 2048 bits, and random wide DAGs — as search, row-major eval and tiled eval
+    kernels, digests and operator values compared row by row.  Every record is inside the tier."""
+    n_q = len(_wide_queries())
+    step = (n_q + WORKERS - 1) // WORKERS
+    tasks = [(str(sim_wide), lo, min(n_q, lo + step)) for lo in range(0, n_q, step)]
+    with mp.get_context("fork").Pool(WORKERS) as pool:
+        results = pool.map(_wide_worker, tasks, chunksize=1)
+    total = {"records": 0, "ok": 0, "outside": 0, "mismatch": 0}
+    for rc, summary, bad, err, n in results:
+        assert summary, f"no summary (rc {rc})\n{err}"
+        assert rc == 0, f"{summary}\n" + "\n".join(bad) + "\n" + err
+        assert int(summary["records"]) == n
+        for k in total:
+            total[k] += int(summary[k])
+    print("wide values:", total)
+    assert total["records"] == 3 * n_q and total["ok"] == total["records"] and total["outside"] == 0, total
+
+
+def _mutants(tmp_path: Path, mutants, wide=()) -> dict:
     """Drivers built with textual edits {name: {file: (old, new)}} of their sources (no sanitizers);
-    the unedited objects are compiled once and shared, everything in parallel."""
+    the unedited objects are compiled once and shared, everything in parallel.  The mutants named
+    in ``wide`` link the C port at -DMAXW=64 (``sim_wide``'s reference)."""
     srcs = ("mythril_amd/csrc/program.cpp", "mythril_amd/csrc/jit_asm.cpp", "tests/asmsim/asmsim_main.cpp",
             "tests/asmsim/asmsim.cpp", "oracle/bveval.c")
     jobs, objs = [], {}
 
-    def compile_(path: Path, o: Path, src: str):
+    def compile_(path: Path, o: Path, src: str, defs=()):
         lang = ["gcc"] if src.endswith(".c") else ["g++", "-std=c++17"]
-        jobs.append(subprocess.Popen(lang + ["-O1", f"-I{ROOT}", f"-I{ROOT / Path(src).parent}", "-I/opt/rocm/include",
-                                             "-c", str(path), "-o", str(o)], stderr=subprocess.PIPE, text=True))
+        jobs.append(subprocess.Popen(lang + ["-O1", *defs, f"-I{ROOT}", f"-I{ROOT / Path(src).parent}",
+                                             "-I/opt/rocm/include", "-c", str(path), "-o", str(o)],
+                                     stderr=subprocess.PIPE, text=True))
+
+    wide_obj = tmp_path / "wide_bveval.c.o"
+    if wide:
+        compile_(ROOT / "oracle/bveval.c", wide_obj, "oracle/bveval.c", [f"-DMAXW={WIDE_MAXW}"])
 
     for src in srcs:
         if any(src not in e for e in mutants.values()):
@@ -524,14 +636,19 @@ def _mutants(tmp_path: Path, mutants) -> dict:
     for name, own in per.items():
         mine = dict(objs)
         mine.update(dict(own))
+        if name in wide:
+            mine["oracle/bveval.c"] = wide_obj
         exe = tmp_path / name
         subprocess.run(["g++"] + [str(mine[s]) for s in srcs] + ["-ldl", "-o", str(exe)], check=True)
         out[name] = exe
     return out
 
 
-def test_the_checks_have_teeth(sim, tmp_path):
-    """The differential catches what it is for.  (1) An emitter with round 4's COPY-liveness bug put
+def test_the_checks_have_teeth(sim, sim_wide, tmp_path):
+    """The differential catches what it is for.  (3, below) A first tier that puts Keccak's closing
+    0x80 pad bit into block 0 instead of the last block is caught by the wide driver's records of
+    136 .. 256 bytes, and by none of the records up to 128 bytes (one block: the same byte) — the
+    gap the suite had before ``test_asm_tier_wide_values_sim``.  (1) An emitter with round 4's COPY-liveness bug put
     back (a MIXED coordinate's COPY branch reusing a copy source the depth-first order had already
     released; it gave false SATs on etherstore on the GPU) fails on etherstore.  (2) A simulator
     whose subtract-with-borrow is wrong reports mismatches: the emitter and the simulator do not
@@ -551,10 +668,24 @@ def test_the_checks_have_teeth(sim, tmp_path):
         "copy_bug": {"mythril_amd/csrc/jit_asm.cpp": ("if (it != cval.end() && val[it->second].def &&",
                                                       "if (it != cval.end() &&")},
         "sub_bug": {"tests/asmsim/asmsim.cpp": ("d[l] = (uint32_t)(u - b);", "d[l] = (uint32_t)(u - b + 1);")},
-    })
+        "keccak_pad_bug": {"mythril_amd/csrc/jit_asm.cpp": ("if (m + k == nblk * 136 - 1) pad |= 0x80u << (8 * k);",
+                                                            "if (m + k == 136 - 1) pad |= 0x80u << (8 * k);")},
+    }, wide=("keccak_pad_bug",))
     rc, summary, lines, _ = run_sim(exes["copy_bug"], eth)
     assert rc != 0 and int(summary["mismatch"]) > 0, (summary, lines)
     mixed = recs("token_transfer_underflow", 1, 1024) + recs("walletlibrary_kill", 1, 1024) + \
         recs("bectoken_batch_overflow", 1, 1024)
     rc, summary, lines, _ = run_sim(exes["sub_bug"], mixed)
     assert rc != 0 and int(summary["mismatch"]) > 0, (summary, lines)
+    from tests.helpers import LENS
+
+    one_block, n_one = _wide_records(_wide_queries(lens=[n for n in LENS if n <= 128]), assemble=False)
+    two_blocks, n_two = _wide_records(_wide_queries(lens=[n for n in LENS if 136 <= n <= 256]), assemble=False)
+    for exe in (sim_wide, exes["keccak_pad_bug"]):
+        rc, summary, lines, _ = run_sim(exe, one_block, {"MYTHGPU_JIT_ASM_CHECK": "1"})
+        assert rc == 0 and int(summary["ok"]) == n_one and int(summary["mismatch"]) == 0, (summary, lines)
+    rc, summary, lines, _ = run_sim(sim_wide, two_blocks, {"MYTHGPU_JIT_ASM_CHECK": "1"})
+    assert rc == 0 and int(summary["ok"]) == n_two, (summary, lines)
+    rc, summary, lines, _ = run_sim(exes["keccak_pad_bug"], two_blocks)
+    # every kernel of every two-block length: search, row-major and tiled eval
+    assert rc != 0 and int(summary["mismatch"]) == n_two, (summary, lines)

@@ -47,8 +47,9 @@ def test_workload_selectors_are_keccak_of_signatures():
 
 def test_cport_keccak_matches_kats_and_python_oracle():
     """The C restatement's Keccak-256 (oracle/bveval.c vkeccak) against the reference's
-    KATs (tests/golden/keccak_kat.json) and oracle/keccak.py on 1..200-byte messages
-    (one and two sponge blocks)."""
+    KATs (tests/golden/keccak_kat.json) and oracle/keccak.py on random messages of 1, 31, 32, 64,
+    100 and 128 bytes (one sponge block: the default library holds 1024 bits; longer inputs and
+    further blocks run on the wide library in tests/test_wide_cpu.py)."""
     import random
 
     from helpers import load_json

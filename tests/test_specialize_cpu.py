@@ -223,3 +223,40 @@ def test_rewritten_random_programs_keep_verdicts(seed):
     want = cport.search(pb, blob, 11 + seed, 0, N, threads=4, verdicts=True)[2]
     got = kops.verdicts(spec, soa, widths, N)
     assert np.array_equal(got, want)
+
+
+def _wide_spec_queries():
+    from tests.helpers import memory_region_queries, wide_literal_tail_query
+
+    qs = {name: roots for name, (roots, _) in memory_region_queries().items()}
+    qs["wide_literal_tail"] = wide_literal_tail_query()
+    return qs
+
+
+@pytest.mark.parametrize("name", sorted(_wide_spec_queries()))
+def test_specialised_wide_programs_keep_verdicts(name):
+    """Above 1024 bits: the memory-region queries (Keccak over a ``Concat`` of literals and symbols,
+    one to two sponge blocks) and 1088-bit literal-tail keys in EQ, ITE and UF keys.  The
+    interpreter's lowering and the compiled kernels' both give the verdicts of the WIDE C port
+    (``cport.search(wide=True)``) on the unspecialised program, on generated candidates of two
+    windows whose reference verdicts hold both values; the interpreter's program compares no
+    literal-tail key at full width."""
+    roots = _wide_spec_queries()[name]
+    P, blob = search.prepare(roots)
+    pb = P.to_bytes()
+    widths = [c.width for c in P.coords]
+    n = 96
+    progs = {interp: native.specialized_program(pb, blob, interp=interp) for interp in (False, True)}
+    if name == "wide_literal_tail":
+        eq_wide = lambda spec: [r for r in spec["code"] if int(r[0]) == kops.K_EQ and int(r[7]) == 1088]  # noqa: E731
+        assert eq_wide(progs[False]) and not eq_wide(progs[True])
+    rng = random.Random(zlib.crc32(name.encode()))
+    for start in (0, (rng.getrandbits(63) & ~0xFFFFFFFF) | 0x80000031):
+        seed = rng.getrandbits(32)
+        soa = cport.gen_soa(pb, blob, seed, start, n, _coord_words(P), wide=True)
+        want = cport.search(pb, blob, seed, start, n, threads=4, verdicts=True, wide=True)[2]
+        assert 0 < int(want.sum()) < n, (name, start, int(want.sum()))
+        for interp, spec in progs.items():
+            got = kops.verdicts(spec, soa, widths, n)
+            bad = np.flatnonzero(got != want)
+            assert bad.size == 0, f"{name} (interp={interp}): verdict differs at index {start + int(bad[0])}"
