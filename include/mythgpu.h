@@ -354,6 +354,40 @@ int mg_search_seeded(uint64_t prog, uint64_t gen, const mg_seed_set_t* seeds, ui
 int mg_eval_seeded(uint64_t prog, uint64_t gen, const mg_seed_set_t* seeds, uint64_t seed, uint64_t start,
                    uint64_t n, uint8_t* verdict_out, uint32_t* watch_out);
 
+/* ---- scored sweep: which candidates came closest ------------------------- *
+ * A seeded sweep that also says how far its candidates were from a hit.
+ * CANDIDATES: exactly the seeded sweep's candidates of (seed, i) above; a null `seeds` or n_seeds = 0
+ *   gives the plain GEN3 stream.  The sweep runs the program's generator-independent lowering (the
+ *   one mg_eval and mg_search_seeded run), on the first device, never split.
+ * VIOLATIONS: viol(i) is the number of DISTINCT ROOT NODES of the program whose value under
+ *   candidate i is 0; a hit is viol = 0.  That lowering emits one assert per distinct root node,
+ *   drops an assert folded to true, may fuse one with its compare and may reorder them; none of
+ *   that changes the count.  If a pass of it ever merges or splits asserts, the scored sweep must
+ *   run a lowering without that pass: this definition is the contract.  A program with more than
+ *   65,535 distinct roots gives MG_E_UNSUPPORTED.
+ * SLOTS: candidate i belongs to slot (i >> 6) mod MG_SCORED_SLOTS (per aligned group, so
+ *   wave-uniform like every per-group choice of GEN3).  Slot s reports the candidate of
+ *   [start, start + count) in that slot with the lowest viol, ties to the lowest index:
+ *   slot_index[s] (UINT64_MAX: no candidate of the window in this slot) and slot_viol[s].  Exact and
+ *   deterministic; nothing depends on timing.
+ * first_hit, n_hits: exactly what mg_search_seeded returns for the same arguments.  With
+ *   MG_SEARCH_EARLY_EXIT first_hit is exact and the slots are exact only when n_hits == 0; without
+ *   it everything is exact.
+ * assign_out (nullable): MG_SCORED_SLOTS x watch_words words; row s is the PROGRAM's watch rows
+ *   (mg_program_info watch_words) of slot s's winner, an empty slot's row is untouched.
+ * Everything is checked before anything is queued: a bad handle, a null res, count > 2^48 and every
+ *   seed-set error mg_search_seeded names give MG_E_INVALID and no launch; count = 0 gives
+ *   {UINT64_MAX, 0} and MG_SCORED_SLOTS empty slots. */
+#define MG_SCORED_SLOTS 32u
+typedef struct mg_scored_res {
+  uint64_t first_hit, n_hits;               /* as mg_search_seeded */
+  uint64_t slot_index[MG_SCORED_SLOTS];     /* UINT64_MAX: no candidate of the window in this slot */
+  uint32_t slot_viol[MG_SCORED_SLOTS];
+} mg_scored_res_t;
+int mg_search_scored(uint64_t prog, uint64_t gen, const mg_seed_set_t* seeds /* nullable */, uint64_t seed,
+                     uint64_t start, uint64_t count, uint32_t flags, mg_scored_res_t* res,
+                     uint32_t* assign_out /* nullable */);
+
 /* ---- JIT specialisation (comgr; hipRTC fallback) -----------------------
  * The compiler runs in a helper process (mythgpu_jitd, next to the library; started on the
  * first compile, MYTHGPU_JIT_ISOLATE=0 compiles in-process): a compiler abort fails that

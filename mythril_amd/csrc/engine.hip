@@ -105,7 +105,10 @@ __device__ __constant__ static const uint32_t kEmptyKeccak[8] = {
 
 // MODE_SEEDED (k_run_seeded): GEN3 candidates with coordinates overridden from a seed set
 // (include/mythgpu.h, "seeded sweep"); SEARCH's reduction plus, when asked, GEN's per-candidate rows
-enum Mode : int { MODE_EVAL = 0, MODE_GEN = 1, MODE_SEARCH = 2, MODE_SEEDED = 3 };
+// MODE_SCORED (k_run_scored): the seeded candidates again, but every assert is evaluated and counted:
+// a lane's violation count, a wave minimum per group and one slot word per (group mod 32)
+// (include/mythgpu.h, "scored sweep")
+enum Mode : int { MODE_EVAL = 0, MODE_GEN = 1, MODE_SEARCH = 2, MODE_SEEDED = 3, MODE_SCORED = 4 };
 
 // Program data (instructions, literals, generator specs) is read-only for a kernel's
 // lifetime.  Reading it through the constant address space lets the compiler use
@@ -400,6 +403,17 @@ struct SeedArgs {
   uint32_t n_seeds, keep16;
 };
 
+// The slot words of a scored sweep (mg_search_scored): MG_SCORED_SLOTS words, one per 128-byte line
+// like the hit stripes (u64 index kSlotStride * s), each the minimum of viol << 48 | (i - start)
+// over the slot's candidates, ~0 when armed.  fetch != 0 is the model launch: block b runs the
+// aligned group of slot b's winner and stores that lane's watch rows at watch[b * watch_words + row].
+constexpr uint32_t kSlotStride = 16;
+constexpr unsigned long long kSlotIndexMask = (1ull << 48) - 1ull;
+struct ScoreArgs {
+  unsigned long long* slots;
+  uint32_t fetch;
+};
+
 // what one aligned group of a seeded sweep takes from the set: seed m, and whether lane 0 replays it
 struct SeedGroup {
   SeedArgs s;
@@ -567,9 +581,10 @@ struct VFG {
 template <class VF, int MODE, int TIER, int KG>
 __device__ __forceinline__ void run_program(const KArgs& k, const VF& vf0, const uint64_t* i, const GKeys* key,
                                             bool early, const bool* active, uint32_t* verdict, uint32_t vb,
-                                            const SeedGroup* sg = nullptr) {
+                                            const SeedGroup* sg = nullptr, uint32_t* viol = nullptr) {
 _Pragma("unroll")
   for (int g = 0; g < KG; g++) verdict[g] = 1;
+  if constexpr (MODE == MODE_SCORED) viol[0] = 0;
   const uint32_t n_instr = k.n_instr;
   // the next instruction's scalar load is issued before this one executes, so its latency
   // overlaps this instruction's LDS traffic instead of adding to it (the code buffer has
@@ -590,7 +605,7 @@ _Pragma("unroll")
       case K_COORD: {
         if (MODE == MODE_EVAL) {
           MG_FOR_G(MG_LIMBS(L, vf.at(in.dst + j) = k.soa[(uint64_t)(in.p1 + j) * k.count + i[g]];););
-        } else if constexpr (MODE == MODE_SEEDED) {
+        } else if constexpr (MODE == MODE_SEEDED || MODE == MODE_SCORED) {
           // the GEN3 value (COPY chains included: a copy is of the source's generated value), then
           // the group's seed over it
           MG_FOR_G({
@@ -728,6 +743,14 @@ _Pragma("unroll")
         break;
       case K_ASSERT_CMP: {
         // a compare whose one use was this assert (program.cpp: fuse_asserts)
+        if constexpr (MODE == MODE_SCORED) {
+          // every lane evaluates every assert: a failed root is counted, never a reason to stop
+          const VFG<VF, KG> vf{vf0, 0};
+          const uint32_t ok = (compare(vf, in.p0 & 0xFFu, in.a, in.b, in.p1) ^ (in.p0 >> 8)) & 1u;
+          verdict[0] &= ok;
+          viol[0] += ok ^ 1u;
+          break;
+        }
         uint64_t any = 0;
         MG_FOR_G({
           verdict[g] &= compare(vf, in.p0 & 0xFFu, in.a, in.b, in.p1) ^ (in.p0 >> 8);
@@ -881,6 +904,13 @@ _Pragma("unroll")
         // every lane of every group failed: stop (verdicts are 0 everywhere).  A loop flag, not a
         // return: a second loop exit made the compiler keep pc in a VGPR (vector address math +
         // readfirstlane per fetch); readfirstlane makes the flag's uniformity explicit
+        if constexpr (MODE == MODE_SCORED) {
+          const VFG<VF, KG> vf{vf0, 0};
+          const uint32_t ok = vf.at(in.a) & 1u;
+          verdict[0] &= ok;
+          viol[0] += ok ^ 1u;
+          break;
+        }
         uint64_t any = 0;
         MG_FOR_G({
           verdict[g] &= vf.at(in.a);
@@ -890,7 +920,14 @@ _Pragma("unroll")
         break;
       }
       case K_WATCH: {
-        if (MODE != MODE_SEARCH && k.watch) {
+        if constexpr (MODE == MODE_SCORED) {
+          // the model launch (ScoreArgs::fetch): the one active lane is the slot's winner
+          if (k.watch && active[0]) {
+            const VFG<VF, KG> vf{vf0, 0};
+            uint32_t* w = k.watch + (uint64_t)vb * k.watch_words + in.p0;
+            for (uint32_t j = 0; j < L; j++) w[j] = vf.at(in.a + j);
+          }
+        } else if (MODE != MODE_SEARCH && k.watch) {
           MG_FOR_G({
             if (active[g])
               for (uint32_t j = 0; j < L; j++) k.watch[(uint64_t)(in.p0 + j) * k.count + i[g]] = vf.at(in.a + j);
@@ -944,6 +981,22 @@ __global__ void __launch_bounds__(kWave) k_run_seeded(KArgs k, SeedArgs sd) {
 #include "run_body.inc"
 #undef MG_VB
 #undef MG_VGRID
+#undef MG_SEEDED
+}
+
+// A scored sweep (mg_search_scored): k_run_seeded's candidates and program in MODE_SCORED.  With
+// sc.fetch the same kernel is the model launch, one block per slot.
+template <class VF, int TIER>
+__global__ void __launch_bounds__(kWave) k_run_scored(KArgs k, SeedArgs sd, ScoreArgs sc) {
+  constexpr int MODE = MODE_SCORED, KG = 1;
+#define MG_SEEDED 1
+#define MG_SCORED 1
+#define MG_VB blockIdx.x
+#define MG_VGRID gridDim.x
+#include "run_body.inc"
+#undef MG_VB
+#undef MG_VGRID
+#undef MG_SCORED
 #undef MG_SEEDED
 }
 
@@ -1268,6 +1321,13 @@ struct Engine {
   uint32_t* d_seed = nullptr;
   uint32_t* h_seed = nullptr;
   size_t seed_words = 0;
+  // mg_search_scored: the slot words (device; pinned: the armed image, then the read-back) and the
+  // 32 winners' watch rows (device, pinned)
+  unsigned long long* d_slots = nullptr;
+  unsigned long long* h_slots = nullptr;
+  uint32_t* d_srows = nullptr;
+  uint32_t* h_srows = nullptr;
+  size_t srows_words = 0;
   mg_stats_t stats{};
   uint64_t refused_base = 0;  // jit_refused_total() at the last mg_stats_reset
 };
@@ -2055,6 +2115,13 @@ static void free_dev_buffers(Engine& e) {
   if (e.h_seed) (void)hipHostFree(e.h_seed);
   e.d_seed = e.h_seed = nullptr;
   e.seed_words = 0;
+  if (e.d_slots) (void)hipFree(e.d_slots);
+  if (e.h_slots) (void)hipHostFree(e.h_slots);
+  if (e.d_srows) (void)hipFree(e.d_srows);
+  if (e.h_srows) (void)hipHostFree(e.h_srows);
+  e.d_slots = e.h_slots = nullptr;
+  e.d_srows = e.h_srows = nullptr;
+  e.srows_words = 0;
   for (int q = 0; q < 4; q++) {
     if (e.xs[q]) (void)hipStreamDestroy(e.xs[q]);
     if (e.xev[q]) (void)hipEventDestroy(e.xev[q]);
@@ -2681,16 +2748,19 @@ static int stage_seeds(Engine& e, const DevProgram& p, const mg_seed_set_t* s, S
 }
 
 // enqueue one k_run_seeded launch of program p (the generator-independent lowering) on e's stream,
-// bracketed by e.ev0 / e.ev1 like launch_async; primary device only, never split
-static int launch_seeded_async(Engine& e, DevProgram& p, const DevGen& g, KArgs k, const SeedArgs& sd, uint64_t count) {
+// bracketed by e.ev0 / e.ev1 like launch_async; primary device only, never split.  With `sc` it is
+// a k_run_scored launch: the sweep, or (sc->fetch) the model launch of one block per slot.
+static int launch_seeded_async(Engine& e, DevProgram& p, const DevGen& g, KArgs k, const SeedArgs& sd, uint64_t count,
+                               const ScoreArgs* sc = nullptr) {
   if (!p.uploaded) {
     int rc = upload_code(e, p);
     if (rc) return rc;
   }
-  const uint64_t lanes = (k.start + count) - (k.start & ~63ull);
+  const bool fetch = sc && sc->fetch;
+  const uint64_t lanes = fetch ? (uint64_t)MG_SCORED_SLOTS * kWave : (k.start + count) - (k.start & ~63ull);
   // the value file's place and the grid: launch_async's rules at one group per wave
   const bool lds = p.lds || (p.low.value_words <= 255u && lanes <= (uint64_t)std::max(e.cu_count, 1) * 2u * kWave);
-  const uint32_t grid = grid_for(e, lanes, lds, p.low.value_words, p.tier);
+  const uint32_t grid = fetch ? MG_SCORED_SLOTS : grid_for(e, lanes, lds, p.low.value_words, p.tier);
   k.specs = g.d_specs;
   k.gconsts = g.d_consts;
   k.n_gconsts = (uint32_t)g.consts.size();
@@ -2718,7 +2788,11 @@ static int launch_seeded_async(Engine& e, DevProgram& p, const DevGen& g, KArgs 
   const size_t shmem = lds ? (size_t)p.low.value_words * kWave * 4 : 0;
   HIPCHK(hipEventRecord(e.ev0, e.stream));
   const dim3 gr(grid), b(kWave);
-#define MG_RUN_SEEDED(VFT, TIERC) hipLaunchKernelGGL((k_run_seeded<VFT, TIERC>), gr, b, shmem, e.stream, k, sd)
+#define MG_RUN_SEEDED(VFT, TIERC)                                                                 \
+  do {                                                                                            \
+    if (sc) hipLaunchKernelGGL((k_run_scored<VFT, TIERC>), gr, b, shmem, e.stream, k, sd, *sc);   \
+    else hipLaunchKernelGGL((k_run_seeded<VFT, TIERC>), gr, b, shmem, e.stream, k, sd);           \
+  } while (0)
   if (lds) {
     if (p.tier == kTierHeavy) MG_RUN_SEEDED(VFLds, kTierHeavy);
     else if (p.tier == kTierMid) MG_RUN_SEEDED(VFLds, kTierMid);
@@ -2812,6 +2886,100 @@ int mg_eval_seeded(uint64_t prog, uint64_t gen, const mg_seed_set_t* seeds, uint
   (void)hipFree(d_ver);
   if (d_watch) (void)hipFree(d_watch);
   return rc;
+}
+
+// the slot words and the winners' rows of a scored sweep, created on first use
+static int ensure_scored(Engine& e, uint32_t ww) {
+  constexpr size_t kWords = (size_t)MG_SCORED_SLOTS * kSlotStride;
+  if (!e.d_slots) {
+    HIPCHK(hipMalloc((void**)&e.d_slots, kWords * sizeof(unsigned long long)));
+    HIPCHK(hipHostMalloc((void**)&e.h_slots, 2 * kWords * sizeof(unsigned long long), hipHostMallocDefault));
+    for (size_t q = 0; q < 2 * kWords; q++) e.h_slots[q] = ~0ull;  // [0, kWords): the armed image
+  }
+  const size_t need = (size_t)MG_SCORED_SLOTS * ww;
+  if (need > e.srows_words) {
+    if (e.d_srows) (void)hipFree(e.d_srows);
+    if (e.h_srows) (void)hipHostFree(e.h_srows);
+    e.d_srows = e.h_srows = nullptr;
+    e.srows_words = 0;
+    HIPCHK(hipMalloc((void**)&e.d_srows, need * 4));
+    HIPCHK(hipHostMalloc((void**)&e.h_srows, need * 4, hipHostMallocDefault));
+    e.srows_words = need;
+  }
+  return MG_OK;
+}
+
+int mg_search_scored(uint64_t prog, uint64_t gen, const mg_seed_set_t* seeds, uint64_t seed, uint64_t start,
+                     uint64_t count, uint32_t flags, mg_scored_res_t* res, uint32_t* assign_out) {
+  Engine& e = E();
+  std::lock_guard<std::mutex> g(e.mu);
+  OnDevice od_(e);
+  // a null set is the empty one: the plain GEN3 stream
+  const mg_seed_set_t none{};
+  if (!seeds) seeds = &none;
+  DevProgram* p;
+  DevGen* dg;
+  int rc = check_seeded(e, prog, gen, seeds, &p, &dg);
+  if (rc) return rc;
+  if (!res) return set_err(MG_E_INVALID, "res: null");
+  if (count > (1ull << 48)) return set_err(MG_E_INVALID, "count above 2^48");
+  // a violation count is 16 bits of the slot word: one assert per distinct root node
+  size_t n_asserts = 0;
+  for (const Instr& in : p->low.code) n_asserts += in.op == K_ASSERT || in.op == K_ASSERT_CMP;
+  if (n_asserts > 65535u) return set_err(MG_E_UNSUPPORTED, "more than 65,535 distinct roots");
+  res->first_hit = ~0ull;
+  res->n_hits = 0;
+  for (uint32_t s = 0; s < MG_SCORED_SLOTS; s++) {
+    res->slot_index[s] = ~0ull;
+    res->slot_viol[s] = 0;
+  }
+  if (count == 0) return MG_OK;
+  constexpr size_t kWords = (size_t)MG_SCORED_SLOTS * kSlotStride;
+  const uint32_t ww = p->low.watch_words;
+  if ((rc = ensure_scored(e, ww))) return rc;
+  SeedArgs sd{};
+  if ((rc = stage_seeds(e, *p, seeds, &sd))) return rc;
+  ScoreArgs sc{e.d_slots, 0u};
+  KArgs k{};
+  k.start = start;
+  k.seed = seed;
+  k.flags = flags & MG_SEARCH_EARLY_EXIT;
+  if ((rc = arm_hits(e))) return rc;
+  // every slot word back to ~0 before every launch: a stale word would win the minimum
+  HIPCHK(hipMemcpyAsync(e.d_slots, e.h_slots, kWords * sizeof(unsigned long long), hipMemcpyHostToDevice, e.stream));
+  if ((rc = launch_seeded_async(e, *p, *dg, k, sd, count, &sc))) return rc;
+  HIPCHK(hipMemcpyAsync(e.h_slots + kWords, e.d_slots, kWords * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                        e.stream));
+  if ((rc = fetch_hits(e))) return rc;
+  unsigned long long hr[2] = {~0ull, 0ull};
+  if ((rc = collect_hits(e, e.stats, count, hr))) return rc;
+  res->first_hit = hr[0];
+  res->n_hits = hr[1];
+  e.stats.hits += hr[1];
+  bool any = false;
+  for (uint32_t s = 0; s < MG_SCORED_SLOTS; s++) {
+    const unsigned long long w = e.h_slots[kWords + (size_t)s * kSlotStride];
+    if (w == ~0ull) continue;
+    res->slot_index[s] = start + (w & kSlotIndexMask);
+    res->slot_viol[s] = (uint32_t)(w >> 48);
+    any = true;
+  }
+  if (!assign_out || ww == 0 || !any) return MG_OK;
+  // the winners' models: one more launch, block b on the group of slot b's winner
+  sc.fetch = 1u;
+  KArgs kf{};
+  kf.start = start;
+  kf.seed = seed;
+  kf.watch = e.d_srows;
+  kf.watch_words = ww;
+  if ((rc = launch_seeded_async(e, *p, *dg, kf, sd, count, &sc))) return rc;
+  HIPCHK(hipMemcpyAsync(e.h_srows, e.d_srows, (size_t)MG_SCORED_SLOTS * ww * 4, hipMemcpyDeviceToHost, e.stream));
+  HIPCHK(hipEventRecord(e.ev2, e.stream));
+  HIPCHK(hipEventSynchronize(e.ev2));
+  for (uint32_t s = 0; s < MG_SCORED_SLOTS; s++)
+    if (res->slot_index[s] != ~0ull)
+      std::memcpy(assign_out + (size_t)s * ww, e.h_srows + (size_t)s * ww, (size_t)ww * 4);
+  return MG_OK;
 }
 
 // an entry mg_search_batch can put into a k_run_batch launch: a latency-bound window (at most two

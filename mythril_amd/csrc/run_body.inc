@@ -1,7 +1,8 @@
   // The body of an interpreter block (engine.hip: k_run, k_run_batch).  The including kernel
   // provides KArgs k, the names VF, MODE, TIER and KG, and the macros MG_VB (the block's id within
   // its launch) and MG_VGRID (that launch's grid size).  k_run_seeded also defines MG_SEEDED and
-  // provides SeedArgs sd (MODE_SEEDED, KG = 1).
+  // provides SeedArgs sd (MODE_SEEDED, KG = 1).  k_run_scored defines both MG_SEEDED and MG_SCORED
+  // and also provides ScoreArgs sc (MODE_SCORED, KG = 1).
   VF vf0(mg_lds, k, MG_VB);
   // the generator constants into LDS behind the value file (one wave per block: its own later
   // reads see the writes, LDS runs a wave's operations in order)
@@ -14,7 +15,7 @@
   const uint64_t total = (MODE == MODE_EVAL) ? k.count : (end - a0);
   // KG groups per wave per pass (run_program): a wave's pass covers KG * 64 consecutive indices
   const uint64_t step = (uint64_t)MG_VGRID * kWave * KG;
-  const bool early = (MODE == MODE_SEARCH || MODE == MODE_SEEDED) && (k.flags & MG_SEARCH_EARLY_EXIT);
+  const bool early = (MODE == MODE_SEARCH || MODE == MODE_SEEDED || MODE == MODE_SCORED) && (k.flags & MG_SEARCH_EARLY_EXIT);
   uint64_t wave_best = ~0ull, wave_hits = 0;  // wave-uniform; published once per wave
   // idx & 63 == threadIdx.x & 63 below (a0 and base are multiples of 64): the lane half of
   // the GEN3 lane key is fixed per thread
@@ -46,7 +47,22 @@
     const auto* c = cst(k.consts) + in.p0;
     MG_FOR_G(MG_LIMBS(L, vf.at(in.dst + j) = c[j];););
   }
+#ifdef MG_SCORED
+  // the sweep walks the window like every other mode; the model launch (sc.fetch) runs one group,
+  // that of slot MG_VB's winner, with only the winner's lane active
+  uint64_t base0 = (uint64_t)MG_VB * kWave, win = ~0ull;
+  if (sc.fetch) {
+    const unsigned long long w = sc.slots[(uint64_t)MG_VB * kSlotStride];
+    win = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(w >> 32)) << 32) |
+          (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)w);
+    if (win == ~0ull) return;  // an empty slot: its row stays as the caller left it
+    win = k.start + (win & kSlotIndexMask);
+    base0 = (win & ~63ull) - a0;
+  }
+  for (uint64_t base = base0; base < total; base += step) {
+#else
   for (uint64_t base = (uint64_t)MG_VB * kWave * KG; base < total; base += step) {
+#endif
     bool active[KG];
     uint64_t i[KG];
     GKeys key[KG];
@@ -57,6 +73,9 @@
       active[g] = (MODE == MODE_EVAL) ? off < total : (idx >= k.start && idx < end);
       // EVAL: SoA row; GEN: output row (only written by active lanes)
       i[g] = (MODE == MODE_EVAL) ? (active[g] ? off : total - 1) : (idx - k.start);
+#ifdef MG_SCORED
+      if (sc.fetch) active[g] = idx == win;
+#endif
     }
     uint64_t cur_u = ~0ull;  // the hit word as this group starts (early exit only)
     if (early) {
@@ -86,7 +105,27 @@
       sgrp[0].m = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(n % ns));
       sgrp[0].replay = n < ns;
     }
+#ifdef MG_SCORED
+    uint32_t viol[1];
+    run_program<VF, MODE, TIER, KG>(k, vf0, i, key, early, active, v, MG_VB, sgrp, viol);
+    if (sc.fetch) return;  // the winner's rows are stored (K_WATCH); nothing to reduce
+    {
+      // the group's best candidate: the minimum of viol << 6 | lane over the active lanes (lowest
+      // violations, then lowest index), six cross-lane steps
+      uint32_t best = active[0] ? (viol[0] << 6) | (threadIdx.x & 63u) : ~0u;
+#pragma unroll
+      for (int o = 1; o < kWave; o <<= 1) best = min(best, (uint32_t)__shfl_xor((int)best, o));
+      if (threadIdx.x == 0 && best != ~0u) {
+        const unsigned long long w =
+            ((unsigned long long)(best >> 6) << 48) | ((a0 + base + (uint64_t)(best & 63u)) - k.start);
+        unsigned long long* sw = sc.slots + (((a0 + base) >> 6) & (MG_SCORED_SLOTS - 1u)) * kSlotStride;
+        // read first, atomicMin only when lower (as the first-hit word)
+        if (w < __hip_atomic_load(sw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(sw, w);
+      }
+    }
+#else
     run_program<VF, MODE, TIER, KG>(k, vf0, i, key, early, active, v, MG_VB, sgrp);
+#endif
 #else
     run_program<VF, MODE, TIER, KG>(k, vf0, i, key, early, active, v, MG_VB);
 #endif
@@ -94,7 +133,7 @@
     for (int g = 0; g < KG; g++) {
       v[g] = active[g] ? v[g] : 0u;
       if (MODE == MODE_SEEDED && k.verdict && active[g]) k.verdict[i[g]] = (uint8_t)v[g];
-      if (MODE == MODE_SEARCH || MODE == MODE_SEEDED) {
+      if (MODE == MODE_SEARCH || MODE == MODE_SEEDED || MODE == MODE_SCORED) {
         const unsigned long long m = __ballot(v[g] != 0);
         if (m) {
           const uint64_t first = a0 + base + (uint64_t)g * kWave + (uint64_t)(__ffsll((long long)m) - 1);
@@ -113,7 +152,7 @@
       }
     }
   }
-  if ((MODE == MODE_SEARCH || MODE == MODE_SEEDED) && threadIdx.x == 0) {
+  if ((MODE == MODE_SEARCH || MODE == MODE_SEEDED || MODE == MODE_SCORED) && threadIdx.x == 0) {
     // a first hit that cannot lower the current minimum is not published; the count goes to the
     // block's stripe (kHitStripes)
     if (wave_best != ~0ull &&

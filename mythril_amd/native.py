@@ -51,7 +51,7 @@ EXPORTS = [
     "mg_init", "mg_collective_kind", "mg_shutdown", "mg_last_error", "mg_version", "mg_program_check", "mg_program_check_gen",
     "mg_program_specialized", "mg_program_load",
     "mg_program_info", "mg_program_free", "mg_gen_load", "mg_gen_info", "mg_gen_free", "mg_eval", "mg_eval_dev",
-    "mg_eval_generated", "mg_search", "mg_search_batch", "mg_search_seeded", "mg_eval_seeded", "mg_keccak256", "mg_stats", "mg_stats_reset", "mg_dev_alloc",
+    "mg_eval_generated", "mg_search", "mg_search_batch", "mg_search_seeded", "mg_eval_seeded", "mg_search_scored", "mg_keccak256", "mg_stats", "mg_stats_reset", "mg_dev_alloc",
     "mg_dev_free", "mg_dev_upload", "mg_dev_download", "mg_program_jit_source", "mg_program_jit_asm", "mg_code_object_check", "mg_jit_compile", "mg_jit_compile_ex", "mg_jit_verdicts", "mg_jit_info", "mg_jit_layout",
     "mg_jit_compile_async", "mg_jit_poll", "mg_jit_cancel", "mg_jit_helper_pid", "mg_cache_clear", "mg_split_range",
     "mg_jit_free", "mg_jit_search", "mg_jit_search_many", "mg_jit_eval", "mg_jit_eval_dev",
@@ -127,6 +127,15 @@ class SeedSet:
 
 
 MG_NONE = 0xFFFFFFFF
+MG_SCORED_SLOTS = 32
+
+
+class ScoredRes(C.Structure):
+    """``mg_scored_res_t``."""
+    _fields_ = [
+        ("first_hit", C.c_uint64), ("n_hits", C.c_uint64),
+        ("slot_index", C.c_uint64 * MG_SCORED_SLOTS), ("slot_viol", C.c_uint32 * MG_SCORED_SLOTS),
+    ]
 
 
 _lib = None
@@ -179,6 +188,8 @@ def load_library(path: Optional[Path] = None) -> C.CDLL:
                                            C.c_uint64, C.c_uint32, u64p, u64p, u32p]),
             "mg_eval_seeded": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(SeedSetC), C.c_uint64, C.c_uint64,
                                          C.c_uint64, u8p, u32p]),
+            "mg_search_scored": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(SeedSetC), C.c_uint64, C.c_uint64,
+                                           C.c_uint64, C.c_uint32, C.POINTER(ScoredRes), u32p]),
             "mg_keccak256": (C.c_int, [u8p, u32p, C.c_uint64, u8p]),
             "mg_stats": (C.c_int, [C.POINTER(Stats)]),
             "mg_stats_reset": (C.c_int, []),
@@ -472,6 +483,29 @@ class Engine:
         _check(self.lib.mg_search_seeded(prog, gen, C.byref(sc), seed, start, count, flags, C.byref(fh),
                                          C.byref(nh), ap))
         return (None if fh.value == NO_HIT else fh.value), nh.value
+
+    def search_scored(self, prog: int, gen: int, seeds: Optional[SeedSet], seed: int, start: int, count: int,
+                      early_exit: bool = False, assigns: Optional[np.ndarray] = None, want_assigns: bool = True):
+        """A scored sweep (``mg_search_scored``): ``(first hit or None, hit count, slots, assigns)``.
+        ``slots`` is a list of 32 ``(index, violations)`` or ``None`` for a slot without a candidate:
+        per slot ``(i >> 6) mod 32`` the window's candidate with the fewest violated distinct roots,
+        ties to the lowest index.  ``assigns`` (uint32[32][watch_words], the PROGRAM's watch rows of
+        each winner; rows of empty slots untouched) is the array passed in, a new zeroed one, or
+        ``None`` with ``want_assigns=False``.  ``seeds=None`` sweeps the plain GEN3 stream."""
+        ww = self.info(prog).watch_words
+        if assigns is None and want_assigns:
+            assigns = np.zeros((MG_SCORED_SLOTS, max(ww, 1)), dtype=np.uint32)
+        if assigns is not None and (assigns.dtype != np.uint32 or not assigns.flags["C_CONTIGUOUS"] or
+                                    assigns.size < MG_SCORED_SLOTS * ww):
+            raise ValueError("search_scored: assigns must be a contiguous uint32 array of 32 x watch_words")
+        res = ScoredRes()
+        sc = seeds.as_c() if seeds is not None else None
+        flags = MG_SEARCH_EARLY_EXIT if early_exit else 0
+        _check(self.lib.mg_search_scored(prog, gen, C.byref(sc) if sc is not None else None, seed, start, count,
+                                         flags, C.byref(res), _ptr(assigns, C.c_uint32) if assigns is not None else None))
+        slots = [None if res.slot_index[s] == NO_HIT else (int(res.slot_index[s]), int(res.slot_viol[s]))
+                 for s in range(MG_SCORED_SLOTS)]
+        return (None if res.first_hit == NO_HIT else int(res.first_hit)), int(res.n_hits), slots, assigns
 
     def eval_seeded(self, prog: int, gen: int, seeds: SeedSet, seed: int, start: int, n: int, watch_words: int = 0):
         """:meth:`eval_generated` over the seeded candidates [start, start + n) (``mg_eval_seeded``)."""

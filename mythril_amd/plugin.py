@@ -86,6 +86,7 @@ class HookStats:
         self.warm_tried = 0        # searches whose first launch was seeded (MYTHGPU_WARM=1)
         self.warm_hits = 0         # ... answered by that launch
         self.warm_replay_hits = 0  # ... by an earlier model replayed as it was
+        self.climb_hits = 0        # searches (or buckets' searches) answered by the climb (MYTHGPU_CLIMB=1)
 
     def __repr__(self):
         return (f"mythgpu: {self.queries} queries, {self.gpu_models} GPU models, {self.fallbacks} to z3 "
@@ -437,7 +438,20 @@ def _warm_kw() -> dict:
     return {"warm": _WARM}
 
 
+def _climb_kw() -> dict:
+    """``{"climb": ClimbConfig()}`` for ``search_partitioned`` under ``MYTHGPU_CLIMB=1`` (default off:
+    {} and the call is what it was): a search whose first launch missed runs one climbing search
+    on violation counts (``search.climb``) before it goes on sampling.  A model found that way is
+    re-checked by z3 like any other."""
+    if os.environ.get("MYTHGPU_CLIMB", "0") != "1":
+        return {}
+    from .search import ClimbConfig
+
+    return {"climb": ClimbConfig()}
+
+
 def _count_warm(res) -> None:
+    STATS.climb_hits += "climb" in str(getattr(res, "engine", ""))
     if "seeded_ms" in getattr(res, "timing", {}):
         STATS.warm_tried += 1
     if getattr(res, "seeded", False):
@@ -452,7 +466,7 @@ def _gpu_search(terms, budget_s, cancel):
     t0 = time.perf_counter()
     try:
         res = search_partitioned(Engine.get(), terms, timeout_s=budget_s, max_candidates=1 << 40,
-                                 cancel=cancel, max_launch_s=RACE_LAUNCH_S, **_warm_kw())
+                                 cancel=cancel, max_launch_s=RACE_LAUNCH_S, **_warm_kw(), **_climb_kw())
     finally:
         STATS.gpu_time += time.perf_counter() - t0
     STATS.candidates += res.scanned
@@ -495,7 +509,8 @@ def _try_gpu(constraints, enforce_execution_time):
         return None
     cs, total, budget = b
     terms = z3bridge.to_terms(cs)
-    res = search_partitioned(Engine.get(), terms, timeout_s=budget / 1000.0, max_candidates=1 << 40, **_warm_kw())
+    res = search_partitioned(Engine.get(), terms, timeout_s=budget / 1000.0, max_candidates=1 << 40, **_warm_kw(),
+                             **_climb_kw())
     STATS.candidates += res.scanned
     _count_warm(res)
     z3m = _confirm(cs, res, total - (time.perf_counter() - t0) * 1e3)

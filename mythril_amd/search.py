@@ -267,6 +267,7 @@ class SearchResult:
         self.buckets = 1
         self.timing = {}
         self.seeded = False  # answered by the seeded first launch (``search(warm=...)``)
+        self.climbed = False  # answered by the climbing search (``search(climb=...)``)
         self.replay = False  # ... by one of its replay lanes: an earlier model as it was
 
 
@@ -536,6 +537,136 @@ def warm_keep16(n_eligible: int) -> int:
     return P16 - int(round(P16 * p))
 
 
+class ClimbConfig:
+    """The climbing search's limits: at most ``rounds`` scored sweeps, a population of at most
+    ``beam`` assignments (the engine takes up to 32 seeds), and ``patience`` rounds in a row that do
+    not lower the best violation count before it gives up."""
+
+    def __init__(self, rounds: int = 16, beam: int = 8, patience: int = 4):
+        if not (rounds >= 1 and 1 <= beam <= 32 and patience >= 1):
+            raise ValueError("ClimbConfig: rounds >= 1, 1 <= beam <= 32, patience >= 1")
+        self.rounds, self.beam, self.patience = int(rounds), int(beam), int(patience)
+
+
+class ClimbResult:
+    """What ``climb`` found.  ``index``: the first hit in the scored index space (None: no hit),
+    ``assign`` its watch rows; ``rounds`` sweeps of ``chunk`` candidates ran (``candidates`` in
+    all); ``best`` is the lowest violation count seen; ``trajectory[r]`` the 32 slots of round r as
+    ``engine.search_scored`` returned them; ``population`` the last population as
+    ``(violations, index, {coordinate: value})``; ``stop`` why it ended ("hit", "rounds",
+    "patience", "cancel", "budget"); ``kernel_ms[r]`` the engine's kernel time of round r's sweep."""
+
+    def __init__(self):
+        self.index = None
+        self.hits = 0
+        self.assign = None
+        self.rounds = 0
+        self.candidates = 0
+        self.best = None
+        self.trajectory: List[list] = []
+        self.population: List[tuple] = []
+        self.stop = None
+        self.kernel_ms: List[float] = []
+
+
+def population_seeds(P: ssa.Program, models: Sequence[Dict[int, int]]):
+    """The seed set (``native.SeedSet``) of a climb population: one seed per ``{coordinate index:
+    value}`` model, every coordinate some model mentions in it, ``keep16 = warm_keep16`` of their
+    number."""
+    from .native import SeedSet
+
+    coord_row = np.full(len(P.coords), NONE, dtype=np.uint32)
+    coord_has = np.zeros(len(P.coords), dtype=np.uint32)
+    rows: List[List[int]] = []
+    for c in P.coords:
+        if _is_lazy(P, c) or not any(c.index in m for m in models):
+            continue
+        coord_row[c.index] = len(rows)
+        for j in range(ssa.limbs(c.width)):
+            rows.append([(int(m.get(c.index, 0)) >> (32 * j)) & 0xFFFFFFFF for m in models])
+        coord_has[c.index] = sum(1 << k for k, m in enumerate(models) if c.index in m)
+    if not rows:
+        return None
+    return SeedSet(np.array(rows, dtype=np.uint32), coord_row, coord_has,
+                   keep16=warm_keep16(int((coord_row != NONE).sum())))
+
+
+def next_population(previous: Sequence[tuple], winners: Sequence[tuple], beam: int) -> List[tuple]:
+    """The climb's population rule.  ``previous`` and ``winners`` (this round's slot winners) hold
+    ``(violations, index, {coordinate: value})``.  The new population is the best ``beam`` DISTINCT
+    assignments among both, ordered by violations, then this round's winners before the previous
+    population (a sideways move replaces its parent), then index."""
+    ranked = sorted([(v, 0, i, m) for v, i, m in winners] + [(v, 1, i, m) for v, i, m in previous],
+                    key=lambda t: t[:3])
+    out, seen = [], set()
+    for v, _, i, m in ranked:
+        key = tuple(sorted(m.items()))
+        if key in seen:
+            continue
+        seen.add(key)
+        out.append((v, i, m))
+        if len(out) == beam:
+            break
+    return out
+
+
+def climb(engine, P: ssa.Program, prog: int, gh: int, seed: int, chunk: int, cfg: Optional[ClimbConfig] = None,
+          cancel=None, seeds=None, deadline: Optional[float] = None) -> ClimbResult:
+    """Stochastic local search on violation counts (``mg_search_scored``).  Round r sweeps
+    ``[r * chunk, (r + 1) * chunk)`` of the scored index space: round 0 unseeded (or from ``seeds``,
+    a ``native.SeedSet``, e.g. ``ModelCache.lookup``), every later round seeded from the population
+    (``population_seeds``), which ``next_population`` rebuilds from each round's 32 slot winners.
+    It stops at a hit, after ``cfg.rounds`` rounds, after ``cfg.patience`` rounds without a lower
+    best, when ``cancel`` is set or ``deadline`` (a ``time.perf_counter`` value) has passed."""
+    cfg = cfg or ClimbConfig()
+    out = ClimbResult()
+    population: List[tuple] = []
+    stale = 0
+    stats = getattr(engine, "stats", None)
+    for r in range(cfg.rounds):
+        if cancel is not None and cancel.is_set():
+            out.stop = "cancel"
+            break
+        if deadline is not None and time.perf_counter() >= deadline:
+            out.stop = "budget"
+            break
+        if r:
+            seeds = population_seeds(P, [m for _, _, m in population])
+        first, nh, slots, assigns = engine.search_scored(prog, gh, seeds, seed, r * chunk, chunk, early_exit=False)
+        out.rounds += 1
+        out.candidates += chunk
+        out.trajectory.append(list(slots))
+        if stats is not None:
+            try:
+                out.kernel_ms.append(float(stats().last_kernel_ms))
+            except Exception:  # a stand-in engine without timing
+                pass
+        if first is not None:
+            out.index, out.hits, out.best, out.stop = first, nh, 0, "hit"
+            out.assign = np.array(assigns[(first >> 6) & 31], dtype=np.uint32)
+            break
+        winners = [(sl[1], sl[0], coords_from_assignment(P, assigns[s])) for s, sl in enumerate(slots) if sl is not None]
+        population = next_population(population, winners, cfg.beam)
+        if not population:
+            out.stop = "rounds"
+            break
+        best = population[0][0]
+        if out.best is None or best < out.best:
+            out.best, stale = best, 0
+        else:
+            stale += 1
+            if stale >= cfg.patience:
+                out.stop = "patience"
+                break
+    else:
+        out.stop = "rounds"
+    out.population = population
+    return out
+
+
+_climb = climb  # ``search(climb=...)`` names its configuration like the function
+
+
 # expected latency of one query-kernel compile (submit -> loadable module), seconds: an
 # exponential average of the compiles this process measured (cold value from the bench:
 # ~0.2 s on the MI355X box's host through hipRTC, less through comgr)
@@ -569,7 +700,7 @@ def search(engine, roots: Sequence[T.Term], seed: int = 0x6D797468, chunk: int =
            max_candidates: int = 1 << 26, timeout_s: float = 10.0, gen: Optional[GenBuilder] = None,
            want_model: bool = True, jit: str = "auto", jit_cost_s: Optional[float] = None,
            cancel=None, max_launch_s: Optional[float] = None, start: int = 0,
-           warm: Optional[ModelCache] = None) -> SearchResult:
+           warm: Optional[ModelCache] = None, climb: Optional[ClimbConfig] = None) -> SearchResult:
     """Find the lowest-index satisfying candidate (or give up: None).
 
     ``jit``: "never" keeps the generic interpreter (``k_run``, no compile latency);
@@ -600,7 +731,16 @@ def search(engine, roots: Sequence[T.Term], seed: int = 0x6D797468, chunk: int =
     whether a replay lane won, ``timing["seeded_ms"]``); a miss continues exactly as without a
     cache, from index 0 of the ordinary stream (the seeded candidates are not counted in
     ``scanned``).  Every hit that returns a model is stored in the cache.  ``warm=None``: nothing
-    of this happens."""
+    of this happens.
+
+    ``climb``: a :class:`ClimbConfig`.  Once the first ordinary launch has missed (an easy query
+    never pays for it), ONE climbing search runs (``climb``: scored sweeps of ``chunk`` candidates
+    seeded from the closest candidates so far).  A hit there ends the search (``engine`` "climb",
+    ``climbed`` True, the index is one of the scored index space); a miss continues the ordinary
+    index stream exactly as without it (the climb's candidates are not counted in ``scanned``).
+    ``timing["climb_ms"]``, ``["climb_rounds"]``, ``["climb_candidates"]``, ``["climb_best"]`` and
+    ``["climb_kernel_ms"]`` say what it cost.  ``climb=None``: nothing of this happens."""
+    climb_cfg = climb  # the parameter hides the function of that name: ``_climb``
     tp = time.perf_counter()
     P, blob = prepare(roots, gen)
     th = time.perf_counter()
@@ -611,7 +751,8 @@ def search(engine, roots: Sequence[T.Term], seed: int = 0x6D797468, chunk: int =
     hit = None
     hits = 0
     used = "interp"
-    seeded = replay = False
+    seeded = replay = climbed = False
+    climb_done = climb_cfg is None
     expected_compile = JIT_COMPILE_S[0] if jit_cost_s is None else jit_cost_s
     expected_asm = JIT_ASM_COMPILE_S[0]
     assign = np.zeros(max(P.watch_words, 1), dtype=np.uint32) if want_model else None
@@ -635,6 +776,7 @@ def search(engine, roots: Sequence[T.Term], seed: int = 0x6D797468, chunk: int =
                     used, tier = "jit", "o3"
                 except Exception:  # the JIT rejected this program: scan on the interpreter
                     jit = "never"
+            chunk0 = chunk  # the first launch's size: the climb's rounds use it too
             if start:
                 chunk = _next_chunk(chunk, jh is not None)
             seeds = warm.lookup(P, roots) if warm is not None and start == 0 else None
@@ -655,6 +797,19 @@ def search(engine, roots: Sequence[T.Term], seed: int = 0x6D797468, chunk: int =
                 left = timeout_s - (now - t0)
                 if left <= 0 or (cancel is not None and cancel.is_set()):
                     break
+                if not climb_done and scanned > 0:
+                    climb_done = True
+                    cr = _climb(engine, P, prog, gh, seed, min(chunk0, max_candidates), climb_cfg, cancel,
+                                   deadline=t0 + timeout_s)
+                    timing["climb_ms"] = (time.perf_counter() - now) * 1e3
+                    timing["climb_rounds"], timing["climb_candidates"] = cr.rounds, cr.candidates
+                    timing["climb_best"], timing["climb_kernel_ms"] = cr.best, cr.kernel_ms
+                    if cr.index is not None:
+                        hit, hits, used, climbed = cr.index, cr.hits, "climb", True
+                        if assign is not None:
+                            assign[:] = cr.assign[:assign.size]
+                        break
+                    continue
                 if ticket_asm is not None:
                     try:
                         h = engine.jit_poll(ticket_asm)
@@ -776,6 +931,7 @@ def search(engine, roots: Sequence[T.Term], seed: int = 0x6D797468, chunk: int =
     res = SearchResult(hit, hits, scanned, dt)
     res.engine = used
     res.seeded, res.replay = seeded, replay
+    res.climbed = climbed
     if tier is not None:
         timing["jit_tier"] = tier
     global LAST_ENGINE, LAST_RESULT
@@ -872,7 +1028,9 @@ def search_partitioned(engine, roots: Sequence[T.Term], timeout_s: float = 10.0,
     the same either way.  Default: off.
 
     ``warm`` (a :class:`ModelCache`, see ``search``) goes to each bucket's search when the buckets
-    are searched one after the other; the batched path ignores it."""
+    are searched one after the other; the batched path ignores it.  ``climb`` (a
+    :class:`ClimbConfig`) goes to every bucket's search on either path; ``climbed`` says whether a
+    climb answered some bucket."""
     from .partition import partition
 
     buckets = partition(roots)
@@ -918,6 +1076,12 @@ def search_partitioned(engine, roots: Sequence[T.Term], timeout_s: float = 10.0,
     # seeded first launches (``warm``): their time summed; seeded / replay when every bucket was
     if any("seeded_ms" in r.timing for r in parts):
         res.timing["seeded_ms"] = sum(r.timing.get("seeded_ms", 0.0) for r in parts)
+    # the buckets' climbs (``climb``): rounds, candidates and time summed, kernel times in order
+    if any("climb_rounds" in r.timing for r in parts):
+        for k in ("climb_ms", "climb_rounds", "climb_candidates"):
+            res.timing[k] = sum(r.timing.get(k, 0) for r in parts)
+        res.timing["climb_kernel_ms"] = [x for r in parts for x in r.timing.get("climb_kernel_ms", [])]
+    res.climbed = any(r.climbed for r in parts)
     res.seeded = all(r.seeded for r in parts)
     res.replay = all(r.replay for r in parts)
     if kw.get("want_model", True):

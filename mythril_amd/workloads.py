@@ -299,3 +299,29 @@ CONFIG = {
 def test_id(name: str) -> str:
     """``C2-token_transfer_underflow``: the config label tests carry in their ids."""
     return f"{CONFIG[name]}-{name}"
+
+
+# ---- conjunctions that need a CONSISTENT assignment (the climbing search's families) ----------
+# Not LASER workloads and not in WORKLOADS: hand-built queries in which every root holds with
+# probability 2^-6 under the default generator and the roots share variables, so plain sampling
+# pays the product of the per-root probabilities (DESIGN.md 3c / 3d).  Raw terms, not Bools.
+CLIMB_ODD = 0x9E3779B97F4A7C15F39CC0605CEDC8341082276BF3A27251F86C6A11D0C18E95
+
+
+def _top6(term, k: int):
+    prod = T.bvbin("bvmul", term, T.BitVecVal(CLIMB_ODD, 256))
+    return T.eq(T.extract(255, 250, prod), T.BitVecVal((11 * k + 5) & 63, 6))
+
+
+def climb_star(n: int = 8, tag: str = "st"):
+    """256-bit y and x_1 .. x_n; roots Extract(255, 250, (x_k + y) * ODD) == c_k.  All share y:
+    one independence bucket."""
+    y = T.BitVecVar(f"{tag}_y", 256)
+    return [_top6(T.bvbin("bvadd", T.BitVecVar(f"{tag}_x{k}", 256), y), k) for k in range(1, n + 1)]
+
+
+def climb_chain(n: int = 8, tag: str = "ch"):
+    """x_0 .. x_n; roots Extract(255, 250, (x_k + x_{k+1}) * ODD) == c_k for k = 0 .. n - 1:
+    repairing an interior root breaks its neighbour."""
+    xs = [T.BitVecVar(f"{tag}_x{k}", 256) for k in range(n + 1)]
+    return [_top6(T.bvbin("bvadd", xs[k], xs[k + 1]), k) for k in range(n)]
