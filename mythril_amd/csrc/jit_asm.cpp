@@ -273,11 +273,22 @@ class Emitter {
     return n;
   }
   std::function<bool()> on_spressure;  // move a Bool value's mask to its VGPR form; true if one went
+  // allocation tags of the SGPR pairs, as vgen for the VGPRs: the mask cache keeps the tag of the pair
+  // it holds, and a hit on a pair released or handed out again since fails the emission
+  std::vector<uint32_t> sgen = std::vector<uint32_t>(kS1, 0);
+  uint32_t sgen_ctr = 0;
+  void scheck(int s, uint32_t tag) const {
+    if (!check_on()) return;
+    if (s < kS0 || s + 1 >= kS1 || sref[s] <= 0 || sgen[s] != tag)
+      fail("internal: cached mask s[" + std::to_string(s) + ":" + std::to_string(s + 1) +
+           "] used after its pair was released or reallocated");
+  }
   int salloc() {
     for (;;) {
       for (int r = kS0; r + 1 < kS1; r += 2)
         if (!sref[r]) {
           sref[r] = 1;
+          sgen[r] = ++sgen_ctr;
           shigh = std::max(shigh, r + 2);
           return r;
         }
@@ -956,9 +967,21 @@ struct Gen {
   // loop) may not run on every path to a later use, so nothing computed there enters the value
   // caches (xcache, litcache): cond counts the open conditional regions
   int cond = 0;
+  // A Bool's mask may not move to its VGPR form under a condition either (spill_mask: the v_cndmask
+  // would be skipped with the region and a later reader compare a register never written), so the
+  // outermost region is entered with SGPR pairs in hand: cache entries go and Bools move before
+  // its first branch.  A region that needs more refuses the kernel (out of SGPRs).
+  static constexpr int kCondPairs = 8;
+  void sreserve() {
+    while (E.sfree() < kCondPairs && E.on_spressure && E.on_spressure()) {
+    }
+  }
   struct CondScope {
     Gen& g;
-    explicit CondScope(Gen& g_) : g(g_) { g.cond++; }
+    explicit CondScope(Gen& g_) : g(g_) {
+      if (!g.cond) g.sreserve();
+      g.cond++;
+    }
     ~CondScope() { g.cond--; }
   };
   // literals materialised in VGPRs, reused while the current constraint's code is emitted (cleared at
@@ -1391,6 +1414,17 @@ struct Gen {
       return true;
     }
     if (cnt != 1 && cnt != n - 1 && n > 32) return false;
+    // the same index register against the same entry set: the mask it gave (the mask cache)
+    MKey ck = idx_key(1, idx);
+    if (!ck.empty()) {
+      ck.push_back(n);
+      for (uint32_t e = 0; e < n; e += 64) {
+        uint64_t w = 0;
+        for (uint32_t q = e; q < n && q < e + 64; q++) w |= (uint64_t)(S[q] != 0) << (q - e);
+        ck.push_back(w);
+      }
+      if (mcache_get(ck, m)) return true;
+    }
     m.k = 2;
     m.s = E.salloc();
     if (cnt == 1 || cnt == n - 1) {
@@ -1402,6 +1436,7 @@ struct Gen {
         E.valu(op + "_e32 vcc, " + hexs(e) + ", " + VL(idx), {}, {kVCC, kVCC + 1});
         E.salu("s_mov_b64 " + SP(m.s) + ", vcc", {m.s, m.s + 1});
       }
+      mcache_put(ck, m);
       return true;
     }
     uint32_t bits = 0;
@@ -1412,6 +1447,7 @@ struct Gen {
     E.valu("v_bfe_u32 " + VL(t) + ", s41, " + VL(idx) + ", 1", {41});
     E.valu("v_cmp_ne_u32_e64 " + SP(m.s) + ", 0, " + VL(t), {}, {m.s, m.s + 1});
     drop(t);
+    mcache_put(ck, m);
     return true;
   }
   // a == b over limb pairs decided by dictionary indices (above); false: the general reduction
@@ -1484,9 +1520,23 @@ struct Gen {
         for (const auto& jj : regs) eq = eq && G[A.off + e * A.Lc + jj.first] == G[B.off + f * B.Lc + jj.second];
         if (eq != (e == f)) return false;
       }
+    MKey ck = idx_key(2, A.idx);
+    {
+      const MKey kb = idx_key(2, B.idx);
+      if (kb.empty()) ck.clear();
+      if (!ck.empty()) {
+        ck.insert(ck.end(), kb.begin() + 1, kb.end());
+        if (std::make_pair(ck[3], ck[4]) < std::make_pair(ck[1], ck[2])) {  // the compare is symmetric
+          std::swap(ck[1], ck[3]);
+          std::swap(ck[2], ck[4]);
+        }
+        if (mcache_get(ck, m)) return true;
+      }
+    }
     m.k = 2;
     m.s = E.salloc();
     E.valu("v_cmp_eq_u32_e64 " + SP(m.s) + ", " + VL(A.idx) + ", " + VL(B.idx), {}, {m.s, m.s + 1});
+    mcache_put(ck, m);
     return true;
   }
   Mask eq_mask(const std::vector<std::pair<Limb, Limb>>& prs, Limb* keep = nullptr) {
@@ -1702,9 +1752,115 @@ struct Gen {
   // keccak site's key against every prior site in each LOOKUP, and in the EQs of the injectivity
   // conditions), and a repeat then costs one compare
   std::map<std::pair<uint32_t, uint32_t>, Limb> eqdiff;  // each entry holds one reference
+
+  // The mask cache: value numbering of the compares' lane masks.  A compare's result is a 64-bit lane
+  // mask in an SGPR pair and no consumer writes a pair in place (every mask operator allocates its
+  // result; ASSERT, the Bool selects and mask_to_vcc only read), so while the operands hold their
+  // values a repeat of the compare is the same pair again: a hit hands it out with a new reference and
+  // emits nothing, where the difference cache above still issued a v_cmp_e64 — the costliest
+  // single-result VALU form — at every use.  Keys: {0, a, b} the value pair of eq_ids; {1, index
+  // register tag, index register, n, entry set} of idx_in_set; {2, tag, register, tag, register} of
+  // dict_eq's index compare.  Each entry holds one reference to its pair and the pair's allocation
+  // tag (checked on a hit under MYTHGPU_JIT_ASM_CHECK).  Entries are made and hit outside conditional
+  // regions only (a pair written under a branch is not defined after the join), go when an operand
+  // value dies (mcache_forget) or an index register's tag is released (mcache_free), and are evicted,
+  // least recently used first, when salloc runs short — before any live Bool moves to its VGPR form.
+  // jit_asm_source's first pass runs without it, as without the other caches.
+  // MYTHGPU_JIT_ASM_NO_MASK_CACHE=1: off.
+  struct MEnt {
+    Mask m;
+    uint32_t tag = 0;
+    uint64_t used = 0;
+  };
+  typedef std::vector<uint64_t> MKey;
+  std::map<MKey, MEnt> mcache;
+  uint32_t mc_hits = 0, mc_evictions = 0, mc_spills = 0;  // the kernel's trailing comment (debug counters)
+  static bool no_mask_cache() {
+    static const bool off = [] {
+      const char* g = getenv("MYTHGPU_JIT_ASM_NO_MASK_CACHE");
+      return g && g[0] == '1';
+    }();
+    return off;
+  }
+  bool mcache_on() const { return lvn_on && caches && !cond && !no_mask_cache(); }
+  bool mcache_get(const MKey& key, Mask& m) {
+    if (key.empty() || !mcache_on()) return false;
+    auto it = mcache.find(key);
+    if (it == mcache.end()) return false;
+    E.scheck(it->second.m.s, it->second.tag);
+    it->second.used = ++tick;
+    m = it->second.m;
+    E.sretain(m);
+    mc_hits++;
+    return true;
+  }
+  void mcache_put(const MKey& key, const Mask& m) {
+    if (key.empty() || m.k != 2 || !mcache_on() || mcache.count(key)) return;
+    MEnt e;
+    e.m = m;
+    e.tag = E.sgen[m.s];
+    e.used = ++tick;
+    E.sretain(m);
+    mcache[key] = e;
+  }
+  bool mcache_evict() {
+    auto best = mcache.end();
+    for (auto it = mcache.begin(); it != mcache.end(); ++it)
+      if (best == mcache.end() || it->second.used < best->second.used) best = it;
+    if (best == mcache.end()) return false;
+    E.srelease(best->second.m);
+    mcache.erase(best);
+    mc_evictions++;
+    return true;
+  }
+  template <class F>
+  void mcache_drop_if(F&& f) {
+    for (auto it = mcache.begin(); it != mcache.end();) {
+      if (f(it->first)) {
+        E.srelease(it->second.m);
+        it = mcache.erase(it);
+      } else {
+        ++it;
+      }
+    }
+  }
+  // value `id` is dead: the masks of its compares go
+  void mcache_forget(uint32_t id) {
+    if (mcache.empty()) return;
+    mcache_drop_if([&](const MKey& k) { return k[0] == 0 && (k[1] == id || k[2] == id); });
+  }
+  // a register's allocation tag died: the masks of compares of it as a dictionary index go
+  void mcache_free(uint32_t g) {
+    if (mcache.empty()) return;
+    mcache_drop_if([&](const MKey& k) { return (k[0] == 1 && k[1] == g) || (k[0] == 2 && (k[1] == g || k[3] == g)); });
+  }
+  // the body's counts, a comment after the kernel's last instruction (tests read them)
+  void mcache_note() {
+    E.o << "  ; mask cache: " << mc_hits << " hits, " << mc_evictions << " evictions, " << mc_spills << " mask spills\n";
+  }
+  // SGPR pairs only the cache holds: free for the asking (salloc evicts them)
+  int mcache_spare() const {
+    int n = 0;
+    for (const auto& kv : mcache) n += E.sref[kv.second.m.s] == 1;
+    return n;
+  }
+  // the key of a compare of `idx` as a dictionary index; empty: not cacheable
+  MKey idx_key(uint64_t kind, const Limb& idx) const {
+    if (!idx.reg() || !idx.g || (int)idx.v < E.vfirst || E.vgen[idx.v] != idx.g) return {};
+    return MKey{kind, idx.g, idx.v};
+  }
+
   Mask eq_ids(uint32_t a, uint32_t b, uint32_t Lk) {
     PinScope pin_(*this, {a, b});
     const auto key = std::minmax(a, b);
+    const MKey mkey{0, key.first, key.second};
+    {
+      Mask hit;
+      if (mcache_get(mkey, hit)) {
+        if (eqdiff.count(key)) eq_last[key] = ++tick;
+        return hit;
+      }
+    }
     auto it = eqdiff.find(key);
     if (it != eqdiff.end()) {
       eq_last[key] = ++tick;
@@ -1712,6 +1868,7 @@ struct Gen {
       m.k = 2;
       m.s = E.salloc();
       E.valu("v_cmp_eq_u32_e64 " + SP(m.s) + ", 0, " + VL(it->second), {}, {m.s, m.s + 1});
+      mcache_put(mkey, m);
       return m;
     }
     std::vector<std::pair<Limb, Limb>> prs;
@@ -1723,6 +1880,7 @@ struct Gen {
       eq_last[key] = ++tick;
     }
     else if (keep.reg()) drop(keep);
+    mcache_put(mkey, m);
     return m;
   }
   // One cache entry goes, to make room under the soft VGPR limit: a literal first (a hit saves one
@@ -1788,7 +1946,7 @@ struct Gen {
     if (annotate) E.o << "  ; vcode " << cur_k << " " << phase << "\n";
   }
   bool spill_mask() {
-    if (cur_k >= code.size()) return false;
+    if (cond || cur_k >= code.size()) return false;
     const Instr& in = code[cur_k];
     auto operand = [&](uint32_t id) {
       if (id == in.a || id == in.b || id == in.c) return true;
@@ -1811,6 +1969,7 @@ struct Gen {
       }
     }
     if (best < 0) return false;
+    mc_spills++;
     limb_of_bool((uint32_t)best);
     E.srelease(val[best].m);
     val[best].m = Mask{};
@@ -4751,7 +4910,7 @@ struct Gen {
           break;
         }
         // (the key tests and their run ORs stay in SGPR pairs over the limbs: only with room for them)
-        if (n >= 2 && n <= 5 && !no_lookup_runs() && E.sfree() >= (int)(n + n * (n - 1) / 2 + 4)) {
+        if (n >= 2 && n <= 5 && !no_lookup_runs() && E.sfree() + mcache_spare() >= (int)(n + n * (n - 1) / 2 + 4)) {
           // The key tests first, then per limb the select chain with runs of priors holding the same
           // limb (a key's literal tail, a zero, the same register) merged into one select under the OR
           // of their tests: applied last to first, h_p ? v : (h_p-1 ? v : c) = (h_p | h_p-1) ? v : c.
@@ -4997,6 +5156,8 @@ struct Gen {
   }
   void body(const std::string& next) {
     eqdiff.clear();  // a kernel abandoned midway (AsmFail: out of VGPRs at this depth) left its entries
+    mcache.clear();
+    mc_hits = mc_evictions = mc_spills = 0;
     mulshare.clear();
     xcache.clear();
     xby.clear();
@@ -5012,13 +5173,15 @@ struct Gen {
       xcache_free(g);
       hcache_free(g);
       dlimb_free(g);
+      mcache_free(g);
     };
     E.on_pressure = [this]() { return evict_one(); };
     E.on_hard = [this]() { return spill_one(); };
     spill_at.assign(val.size(), {});
     slot_busy.clear();
     pinned.clear();
-    E.on_spressure = [this]() { return spill_mask(); };
+    // short of SGPR pairs: the mask cache's entries go first, then a live Bool moves to its VGPR form
+    E.on_spressure = [this]() { return mcache_evict() || spill_mask(); };
     lvn_on = true;
     static const bool annotate = getenv("MYTHGPU_JIT_ASM_ANNOTATE") != nullptr;
     for (size_t k = 0; k < code.size(); k++) {
@@ -5058,6 +5221,7 @@ struct Gen {
           kill(id);
           val[id].def = false;
           if (!eqdiff.empty()) eq_forget(id);
+          mcache_forget(id);
         }
       };
       if (in.dst != MG_NONE && in.dst < last.size() && last[in.dst] < 0) done(in.dst);
@@ -5100,6 +5264,7 @@ struct Gen {
     mulshare.clear();
     for (auto& kv : eqdiff) drop(kv.second);  // values live to the end of the body
     eqdiff.clear();
+    mcache_drop_if([](const MKey&) { return true; });
     xcache_clear();
     litcache_clear();
     lvn_on = false;
@@ -5587,6 +5752,7 @@ struct Gen {
     E.label(exit_);
     E.ctl("s_waitcnt vmcnt(0)");  // the last iteration's loads for a group past n
     E.ctl("s_endpgm");
+    mcache_note();
     const int nv = std::max(E.vhigh, kV0), ns = std::max(E.shigh, rp_used ? 102 : 56);
     const int accum = (nv + 3) / 4 * 4;
     o << "  .section .rodata,\"a\",@progbits\n  .p2align 6, 0x0\n  .amdhsa_kernel " << name << "\n"
@@ -5912,6 +6078,7 @@ struct Gen {
       E.label(end);
     }
     E.ctl("s_endpgm");
+    mcache_note();
     // descriptor (MYTHGPU_JIT_ASM_DIAG_VGPRS=N: at least N VGPRs reserved — fewer waves per SIMD, for
     // occupancy-sensitivity timing builds)
     static const int diag_vgprs = [] {

@@ -451,6 +451,70 @@ std::vector<VInstr> fold_not_compares(const std::vector<VInstr>& code, size_t nv
   return r;
 }
 
+// Value numbering of the specialised lists (both the compiled kernels' and the interpreter's), after
+// the rewrites above and the heavy-last ordering: a pure instruction whose (op, width, a, b, c, p0,
+// p1) — a LOOKUP's prior list in place of its aux offset — equals an earlier one's, with the renames
+// so far applied and the operands of the commutative operators (EQ, AND, OR, XOR, ADD, MUL) in
+// ascending order, is dropped and its readers read the earlier value; a second ASSERT of one value
+// goes too.  The list is straight-line SSA, so the earlier definition reaches every reader of the
+// later one.  push_eq_into_lookup creates the same EQ(v_q, x) once per prior and LASER repeats its
+// injectivity conditions per site, so real programs hold such repeats (C2 one EQ, C4 nine
+// instructions).  Literals and coordinates stay (a CONST names its words, a COORD its generator).
+// MYTHGPU_GVN=0: off.
+std::vector<VInstr> value_number(const std::vector<VInstr>& code, size_t nv) {
+  static const bool on = [] {
+    const char* g = getenv("MYTHGPU_GVN");
+    return !(g && g[0] == '0');
+  }();
+  if (!on) return code;
+  const uint32_t NONE = MG_NONE;
+  std::vector<uint32_t> rep(nv);
+  for (size_t v = 0; v < nv; v++) rep[v] = (uint32_t)v;
+  auto R = [&](uint32_t v) { return v != NONE && v < nv ? rep[v] : v; };
+  std::map<std::vector<uint32_t>, uint32_t> seen;  // canonical key -> the surviving value
+  std::set<uint32_t> asserted;
+  std::vector<VInstr> out;
+  out.reserve(code.size());
+  for (const VInstr& c0 : code) {
+    VInstr c = c0;
+    if (c.op == K_LOOKUP) {
+      c.a = R(c.a);
+      c.p0 = R(c.p0);
+      for (uint32_t& v : c.prior) v = R(v);
+    } else if (c.op == K_CONCAT || c.op == K_EXTRACT || c.op == K_ZEXT || c.op == K_SEXT || c.op == K_KECCAK ||
+               c.op == K_ASSERT || c.op == K_WATCH || c.op == K_COPY) {
+      c.a = R(c.a);
+      c.b = R(c.b);
+    } else if (c.op != K_CONST && c.op != K_COORD) {
+      c.a = R(c.a);
+      c.b = R(c.b);
+      c.c = R(c.c);
+    }
+    if (c.op == K_ASSERT) {
+      if (!asserted.insert(c.a).second) continue;
+      out.push_back(std::move(c));
+      continue;
+    }
+    const bool pure = c.op != K_CONST && c.op != K_COORD && c.op != K_WATCH && c.op != K_ASSERT_CMP && c.dst != NONE &&
+                      c.dst < nv;
+    if (!pure) {
+      out.push_back(std::move(c));
+      continue;
+    }
+    if ((c.op == K_EQ || c.op == K_AND || c.op == K_OR || c.op == K_XOR || c.op == K_ADD || c.op == K_MUL) && c.a > c.b)
+      std::swap(c.a, c.b);
+    std::vector<uint32_t> key{c.op, c.wd, c.a, c.b, c.c, c.p0, c.op == K_LOOKUP ? 0u : c.p1};
+    key.insert(key.end(), c.prior.begin(), c.prior.end());
+    auto ins = seen.emplace(std::move(key), c.dst);
+    if (!ins.second) {
+      rep[c.dst] = ins.first->second;
+      continue;
+    }
+    out.push_back(std::move(c));
+  }
+  return out;
+}
+
 std::vector<VInstr> sink_inputs(const std::vector<VInstr>& code, size_t nv) {
   std::vector<int64_t> first(nv, -1);
   for (size_t k = 0; k < code.size(); k++)
@@ -2704,10 +2768,14 @@ int specialize_program(const Lowered& in, const std::vector<GenSpec>* specs, con
     if (narrowed) {
       std::vector<VInstr> kept_wide = jit_rewrites(dce(wide));
       if (order) heavy_last(kept_wide);
+      kept_wide = value_number(kept_wide, vwidth.size());
+      kept = value_number(kept, vwidth.size());
       allocate(kept_wide, vwidth, out, &kept);
     } else {
       std::vector<VInstr> jit_list = jit_rewrites(kept);
       if (order) heavy_last(jit_list);
+      jit_list = value_number(jit_list, vwidth.size());
+      kept = value_number(kept, vwidth.size());
       if (pushed || pruned || folded)
         allocate(jit_list, vwidth, out, &kept);
       else
