@@ -388,6 +388,80 @@ int mg_search_scored(uint64_t prog, uint64_t gen, const mg_seed_set_t* seeds /* 
                      uint64_t start, uint64_t count, uint32_t flags, mg_scored_res_t* res,
                      uint32_t* assign_out /* nullable */);
 
+/* ---- the climb on the device: a whole climbing search in one call ---------- *
+ * The search of mythril_amd/search.py `climb`, round for round, with the step between two rounds on
+ * the GPU (kernel k_climb_select) and no host wait inside a burst of rounds.
+ * ROUND r (r = 0 .. rounds - 1) is the scored sweep of [r * chunk, (r + 1) * chunk) under `seed`
+ *   without MG_SEARCH_EARLY_EXIT, then the model launch of its 32 slot winners.  Round 0 takes `seeds`
+ *   (nullable: the plain GEN3 stream; any layout, as for mg_search_scored).  Round r >= 1 takes the
+ *   POPULATION after round r - 1 as its seed set, laid out by the ROW MAP, with `keep16` and every
+ *   mapped coordinate present in every seed.
+ * ROW MAP: coord_row[c] (n_coords words, MG_NONE = never seeded) is the first seed row of coordinate
+ *   c; seed row r of a candidate is word watch_row[r] of its PROGRAM watch rows (n_rows words).  The
+ *   map is the same for every round.
+ * POPULATION after a round without a hit: the candidates are the round's non-empty slot winners and
+ *   the previous members; order them by violations, then this round's winners before previous
+ *   members, then the lower index; walk that order and keep a candidate iff its n_rows seed rows
+ *   differ from those of every candidate kept so far; stop at `beam`.  `best` is the lowest violation
+ *   count of any population's first member (0 on a hit, UINT32_MAX: none).
+ * STOP (mg_climb_res_t.stop): MG_CLIMB_HIT, a round's first_hit is not UINT64_MAX (the population
+ *   stays that of the round before); MG_CLIMB_EMPTY, a round left no candidate; MG_CLIMB_PATIENCE,
+ *   `patience` rounds in a row whose population did not lower `best`; MG_CLIMB_ROUNDS, `rounds`
+ *   rounds ran (tested in that order after each round); MG_CLIMB_CANCEL / MG_CLIMB_BUDGET, see bursts.
+ * BURSTS: rounds are queued on the engine's stream min(burst, 64) at a time: sweep, model launch,
+ *   population step, repeat, with one host wait per burst.  Before every burst the host reads
+ *   *cancel (nullable; nonzero stops with MG_CLIMB_CANCEL) and the clock (*budget_s, nullable:
+ *   seconds from the call's entry; at or past it, MG_CLIMB_BUDGET), in that order; so a climb whose
+ *   cancel word is set, or whose budget is <= 0, at entry runs 0 rounds and launches nothing.
+ *   Launches of a burst that follow the climb's end return at once.
+ * RESULTS: res (below); assign_out (nullable, watch_words words): on a hit the hit's watch rows, those
+ *   of slot (first_hit >> 6) mod 32; traj_index / traj_viol (nullable, rounds x 32 each): the slots of
+ *   every round that ran, UINT64_MAX / 0 for an empty slot; pop_rows (nullable, n_rows x 32 words):
+ *   the final population's seed rows, row r of member m at pop_rows[r * n_pop + m]; burst_ms
+ *   (nullable, `rounds` doubles): the kernel time of each burst, from the engine's events.
+ *   mg_stats counts one launch and `chunk` candidates per round that ran; last_kernel_ms is the last
+ *   burst's time.  It runs on the first device and is never split.
+ * Everything is checked before anything is queued, and a failed check launches nothing:
+ *   MG_E_INVALID for every error of mg_search_scored, a null args / res / coord_row / watch_row,
+ *   rounds = 0, beam outside 1..32, patience = 0, burst = 0, chunk = 0, rounds * chunk > 2^48,
+ *   n_rows = 0, keep16 > 65536, a watch_row entry >= watch_words, a mapped coordinate whose limbs
+ *   run past n_rows; MG_E_UNSUPPORTED for a program with watch_words = 0. */
+#define MG_CLIMB_HIT 1u
+#define MG_CLIMB_PATIENCE 2u
+#define MG_CLIMB_ROUNDS 3u
+#define MG_CLIMB_EMPTY 4u
+#define MG_CLIMB_CANCEL 5u
+#define MG_CLIMB_BUDGET 6u
+typedef struct mg_climb_args {
+  const mg_seed_set_t* seeds; /* round 0, nullable */
+  const uint32_t* coord_row;  /* n_coords */
+  const uint32_t* watch_row;  /* n_rows */
+  uint32_t n_rows, keep16;
+  uint64_t seed, chunk, rounds;
+  uint32_t beam, patience, burst, reserved;
+  const volatile uint32_t* cancel; /* nullable, host memory */
+  const double* budget_s;          /* nullable */
+} mg_climb_args_t;
+typedef struct mg_climb_res {
+  uint64_t first_hit, n_hits; /* of the round that hit, else UINT64_MAX / 0 */
+  uint64_t rounds_run;
+  uint32_t best, stop, n_pop, n_bursts;
+  uint64_t pop_index[MG_SCORED_SLOTS];
+  uint32_t pop_viol[MG_SCORED_SLOTS];
+} mg_climb_res_t;
+int mg_search_climb(uint64_t prog, uint64_t gen, const mg_climb_args_t* args, mg_climb_res_t* res,
+                    uint32_t* assign_out, uint64_t* traj_index, uint32_t* traj_viol, uint32_t* pop_rows,
+                    double* burst_ms);
+/* host-only (no GPU needed): one population step, the function k_climb_select runs, over host
+ * arrays.  slot_words: the round's 32 slot words (viol << 48 | i - start, UINT64_MAX empty); srows:
+ * 32 x watch_words; prev_rows: n_rows x n_prev.  Writes *n_out members: out_viol / out_index (32
+ * each) and out_rows (n_rows x *n_out, capacity n_rows x 32). */
+int mg_climb_select_host(const uint64_t* slot_words, const uint32_t* srows, uint32_t watch_words,
+                         const uint32_t* watch_row, uint32_t n_rows, uint64_t start, uint32_t n_prev,
+                         const uint32_t* prev_viol, const uint64_t* prev_index, const uint32_t* prev_rows,
+                         uint32_t beam, uint32_t* n_out, uint32_t* out_viol, uint64_t* out_index,
+                         uint32_t* out_rows);
+
 /* ---- JIT specialisation (comgr; hipRTC fallback) -----------------------
  * The compiler runs in a helper process (mythgpu_jitd, next to the library; started on the
  * first compile, MYTHGPU_JIT_ISOLATE=0 compiles in-process): a compiler abort fails that

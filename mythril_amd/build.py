@@ -20,7 +20,7 @@ JITD_SOURCES = [CSRC / "jitd.cpp", CSRC / "jit.cpp", CSRC / "program.cpp"]
 
 SOURCES = [CSRC / "engine.hip", CSRC / "program.cpp", CSRC / "jit.cpp", CSRC / "jit_asm.cpp"]
 HEADERS = [CSRC / "bv_device.h", CSRC / "keccak_device.h", CSRC / "gen_device.h", CSRC / "jit_device.h", CSRC / "program.hpp",
-           CSRC / "jit.hpp", CSRC / "run_body.inc", INCLUDE / "mythgpu.h"]
+           CSRC / "jit.hpp", CSRC / "run_body.inc", CSRC / "climb_select.h", INCLUDE / "mythgpu.h"]
 PRELUDE_PARTS = [CSRC / "bv_device.h", CSRC / "keccak_device.h", CSRC / "gen_device.h", CSRC / "jit_device.h"]
 PRELUDE_INC = CSRC / "jit_prelude.inc"
 

@@ -34,6 +34,7 @@
 
 #include "../../include/mythgpu.h"
 #include "bv_device.h"
+#include "climb_select.h"
 #include "keccak_device.h"
 #include "gen_device.h"
 #include "jit.hpp"
@@ -1000,6 +1001,118 @@ __global__ void __launch_bounds__(kWave) k_run_scored(KArgs k, SeedArgs sd, Scor
 #undef MG_SEEDED
 }
 
+// ---- the climb on the device (mg_search_climb) -------------------------------------------------
+// The control block of a climb in flight: the population between rounds and why the climb ended.
+// k_climb_select writes it, k_run_climb reads `done` and `n_seeds`, the host reads it per burst.
+struct ClimbCtl {
+  uint32_t n_seeds;     // members of the population = seeds of the next sweep
+  uint32_t best;        // lowest violation count so far, ~0: none yet
+  uint32_t stale;       // rounds in a row that did not lower it
+  uint32_t rounds_run;
+  uint32_t done;        // 0, or MG_CLIMB_HIT / _PATIENCE / _ROUNDS / _EMPTY
+  uint32_t cur;         // which of the two row buffers holds the population's seed rows
+  uint32_t pad[2];
+  unsigned long long first_hit, n_hits;
+  unsigned long long pop_index[MG_SCORED_SLOTS];
+  uint32_t pop_viol[MG_SCORED_SLOTS];
+};
+struct ClimbArgs {
+  const ClimbCtl* ctl;
+  uint32_t from_ctl;  // rounds >= 1: the seed count is the population's
+};
+
+// A round's sweep or model launch inside a burst: k_run_scored's block body, but a block returns at
+// once when the climb has ended, and from round 1 on the number of seeds is the control block's.
+template <class VF, int TIER>
+__global__ void __launch_bounds__(kWave) k_run_climb(KArgs k, SeedArgs sd, ScoreArgs sc, ClimbArgs cl) {
+  constexpr int MODE = MODE_SCORED, KG = 1;
+  if (__builtin_amdgcn_readfirstlane((int)cl.ctl->done)) return;
+  if (cl.from_ctl) sd.n_seeds = (uint32_t)__builtin_amdgcn_readfirstlane((int)cl.ctl->n_seeds);
+#define MG_SEEDED 1
+#define MG_SCORED 1
+#define MG_VB blockIdx.x
+#define MG_VGRID gridDim.x
+#include "run_body.inc"
+#undef MG_VB
+#undef MG_VGRID
+#undef MG_SCORED
+#undef MG_SEEDED
+}
+
+struct ClimbSel {
+  ClimbCtl* ctl;
+  unsigned long long* slots;  // the round's slot words (kSlotStride apart)
+  unsigned long long* hit;    // the hit buffer: first hit, count, count stripes
+  const uint32_t* srows;      // the winners' watch rows, [32][ww]
+  const uint32_t* watch_row;  // the row map, [n_rows]
+  const uint32_t* prev_rows;  // the previous population's seed rows
+  uint32_t* new_rows;         // ... and where the new one's go (the other buffer)
+  unsigned long long* traj;   // this round's 32 words of the trajectory
+  uint32_t* hit_rows;         // [ww]
+  unsigned long long start;   // the round's window starts here
+  uint32_t ww, n_rows, beam, patience, rounds, cur;
+};
+
+// The step between two rounds, one wave: after round r's sweep and model launch it ends the climb
+// (a hit, patience, the last round) or builds the population and seed set of round r + 1
+// (climb_select.h), then re-arms the slot words and the hit buffer for that round.
+__global__ void __launch_bounds__(kWave) k_climb_select(ClimbSel a) {
+  __shared__ ClimbWork w;
+  ClimbCtl* ctl = a.ctl;
+  if (ctl->done) return;
+  const uint32_t lane = threadIdx.x;
+  const unsigned long long first = a.hit[0];
+  if (lane < MG_SCORED_SLOTS) a.traj[lane] = a.slots[(size_t)lane * kSlotStride];
+  if (first != ~0ull) {
+    unsigned long long nh = a.hit[1];
+    for (uint32_t q = 1; q <= kHitStripes; q++) nh += a.hit[kHitStride * q];
+    const uint32_t slot = (uint32_t)(first >> 6) & (MG_SCORED_SLOTS - 1u);
+    for (uint32_t j = lane; j < a.ww; j += kWave) a.hit_rows[j] = a.srows[(size_t)slot * a.ww + j];
+    if (lane == 0) {
+      ctl->first_hit = first;
+      ctl->n_hits = nh;
+      ctl->best = 0;
+      ctl->rounds_run += 1;
+      ctl->done = MG_CLIMB_HIT;
+    }
+  } else {
+    const ClimbRows R{a.srows, a.watch_row, a.prev_rows, a.ww, ctl->n_seeds};
+    mg_climb_select(R, a.slots, kSlotStride, a.start, ctl->pop_viol, ctl->pop_index, a.n_rows, a.beam, w, a.new_rows);
+    __syncthreads();
+    const uint32_t nk = w.n_kept;
+    if (lane < nk) {
+      ctl->pop_viol[lane] = w.viol[w.kept[lane]];
+      ctl->pop_index[lane] = w.index[w.kept[lane]];
+    }
+    if (lane == 0) {
+      const uint32_t rr = ctl->rounds_run + 1;
+      uint32_t done = 0;
+      ctl->n_seeds = nk;
+      ctl->cur = a.cur;
+      ctl->rounds_run = rr;
+      if (nk == 0) {
+        done = MG_CLIMB_EMPTY;
+      } else {
+        const uint32_t b = w.viol[w.kept[0]];
+        if (ctl->best == ~0u || b < ctl->best) {
+          ctl->best = b;
+          ctl->stale = 0;
+        } else {
+          const uint32_t st = ctl->stale + 1;
+          ctl->stale = st;
+          if (st >= a.patience) done = MG_CLIMB_PATIENCE;
+        }
+      }
+      if (!done && rr >= a.rounds) done = MG_CLIMB_ROUNDS;
+      ctl->done = done;
+    }
+  }
+  __syncthreads();  // every read of the round's words is done: arm them for the next round
+  if (lane < MG_SCORED_SLOTS) a.slots[(size_t)lane * kSlotStride] = ~0ull;
+  if (lane <= kHitStripes) a.hit[lane ? kHitStride * lane : 1u] = 0ull;
+  if (lane == 0) a.hit[0] = ~0ull;
+}
+
 // One entry of a batched search launch (mg_search_batch): the arguments of one query's SEARCH
 // launch and the run of physical blocks [block0, block0 + nblocks) that sweeps it.  Entries are in
 // block order and cover the grid without gaps.
@@ -1328,6 +1441,11 @@ struct Engine {
   uint32_t* d_srows = nullptr;
   uint32_t* h_srows = nullptr;
   size_t srows_words = 0;
+  // mg_search_climb: control block, trajectory, hit rows, the two seed-row buffers and the row map
+  // (device; pinned: the image uploaded at the start, then the per-burst read-back)
+  uint32_t* d_climb = nullptr;
+  uint32_t* h_climb = nullptr;
+  size_t climb_words = 0;
   mg_stats_t stats{};
   uint64_t refused_base = 0;  // jit_refused_total() at the last mg_stats_reset
 };
@@ -2122,6 +2240,10 @@ static void free_dev_buffers(Engine& e) {
   e.d_slots = e.h_slots = nullptr;
   e.d_srows = e.h_srows = nullptr;
   e.srows_words = 0;
+  if (e.d_climb) (void)hipFree(e.d_climb);
+  if (e.h_climb) (void)hipHostFree(e.h_climb);
+  e.d_climb = e.h_climb = nullptr;
+  e.climb_words = 0;
   for (int q = 0; q < 4; q++) {
     if (e.xs[q]) (void)hipStreamDestroy(e.xs[q]);
     if (e.xev[q]) (void)hipEventDestroy(e.xev[q]);
@@ -2749,9 +2871,11 @@ static int stage_seeds(Engine& e, const DevProgram& p, const mg_seed_set_t* s, S
 
 // enqueue one k_run_seeded launch of program p (the generator-independent lowering) on e's stream,
 // bracketed by e.ev0 / e.ev1 like launch_async; primary device only, never split.  With `sc` it is
-// a k_run_scored launch: the sweep, or (sc->fetch) the model launch of one block per slot.
+// a k_run_scored launch: the sweep, or (sc->fetch) the model launch of one block per slot.  With
+// `cl` too it is a k_run_climb launch inside a burst (mg_search_climb), which brackets the whole
+// burst with the events itself.
 static int launch_seeded_async(Engine& e, DevProgram& p, const DevGen& g, KArgs k, const SeedArgs& sd, uint64_t count,
-                               const ScoreArgs* sc = nullptr) {
+                               const ScoreArgs* sc = nullptr, const ClimbArgs* cl = nullptr) {
   if (!p.uploaded) {
     int rc = upload_code(e, p);
     if (rc) return rc;
@@ -2786,11 +2910,12 @@ static int launch_seeded_async(Engine& e, DevProgram& p, const DevGen& g, KArgs 
     k.scratch = e.d_scratch;
   }
   const size_t shmem = lds ? (size_t)p.low.value_words * kWave * 4 : 0;
-  HIPCHK(hipEventRecord(e.ev0, e.stream));
+  if (!cl) HIPCHK(hipEventRecord(e.ev0, e.stream));
   const dim3 gr(grid), b(kWave);
 #define MG_RUN_SEEDED(VFT, TIERC)                                                                 \
   do {                                                                                            \
-    if (sc) hipLaunchKernelGGL((k_run_scored<VFT, TIERC>), gr, b, shmem, e.stream, k, sd, *sc);   \
+    if (cl) hipLaunchKernelGGL((k_run_climb<VFT, TIERC>), gr, b, shmem, e.stream, k, sd, *sc, *cl); \
+    else if (sc) hipLaunchKernelGGL((k_run_scored<VFT, TIERC>), gr, b, shmem, e.stream, k, sd, *sc);   \
     else hipLaunchKernelGGL((k_run_seeded<VFT, TIERC>), gr, b, shmem, e.stream, k, sd);           \
   } while (0)
   if (lds) {
@@ -2804,7 +2929,7 @@ static int launch_seeded_async(Engine& e, DevProgram& p, const DevGen& g, KArgs 
   }
 #undef MG_RUN_SEEDED
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(e.ev1, e.stream));
+  if (!cl) HIPCHK(hipEventRecord(e.ev1, e.stream));
   return MG_OK;
 }
 
@@ -2979,6 +3104,207 @@ int mg_search_scored(uint64_t prog, uint64_t gen, const mg_seed_set_t* seeds, ui
   for (uint32_t s = 0; s < MG_SCORED_SLOTS; s++)
     if (res->slot_index[s] != ~0ull)
       std::memcpy(assign_out + (size_t)s * ww, e.h_srows + (size_t)s * ww, (size_t)ww * 4);
+  return MG_OK;
+}
+
+// ---- the climb on the device (mg_search_climb) --------------------------------------------------
+
+constexpr uint32_t kClimbBurstMax = 64;
+
+int mg_search_climb(uint64_t prog, uint64_t gen, const mg_climb_args_t* a, mg_climb_res_t* res, uint32_t* assign_out,
+                    uint64_t* traj_index, uint32_t* traj_viol, uint32_t* pop_rows, double* burst_ms) {
+  const auto t_entry = std::chrono::steady_clock::now();
+  Engine& e = E();
+  std::lock_guard<std::mutex> g(e.mu);
+  OnDevice od_(e);
+  if (!a) return set_err(MG_E_INVALID, "args: null");
+  const mg_seed_set_t none{};
+  const mg_seed_set_t* seeds = a->seeds ? a->seeds : &none;
+  DevProgram* p;
+  DevGen* dg;
+  int rc = check_seeded(e, prog, gen, seeds, &p, &dg);
+  if (rc) return rc;
+  if (!res) return set_err(MG_E_INVALID, "res: null");
+  if (a->rounds == 0 || a->patience == 0 || a->burst == 0 || a->chunk == 0)
+    return set_err(MG_E_INVALID, "climb: rounds, patience, burst and chunk must be at least 1");
+  if (a->beam < 1u || a->beam > MG_SCORED_SLOTS) return set_err(MG_E_INVALID, "climb: beam outside 1..32");
+  if (a->chunk > (1ull << 48) || a->rounds > (1ull << 48) / a->chunk)
+    return set_err(MG_E_INVALID, "climb: rounds * chunk above 2^48");
+  if (a->keep16 > 65536u) return set_err(MG_E_INVALID, "climb: keep16 above 65536");
+  size_t n_asserts = 0;
+  for (const Instr& in : p->low.code) n_asserts += in.op == K_ASSERT || in.op == K_ASSERT_CMP;
+  if (n_asserts > 65535u) return set_err(MG_E_UNSUPPORTED, "more than 65,535 distinct roots");
+  const uint32_t ww = p->low.watch_words, nc = p->low.n_coords, n_rows = a->n_rows;
+  if (ww == 0) return set_err(MG_E_UNSUPPORTED, "climb: the program has no watch rows");
+  if (!a->coord_row || !a->watch_row || n_rows == 0) return set_err(MG_E_INVALID, "climb: null or empty row map");
+  for (uint32_t r = 0; r < n_rows; r++)
+    if (a->watch_row[r] >= ww) return set_err(MG_E_INVALID, "climb: watch_row entry past watch_words");
+  for (uint32_t c = 0; c < nc; c++) {
+    const uint32_t r = a->coord_row[c];
+    if (r == MG_NONE) continue;
+    const uint32_t L = (p->low.coord_width[c] + 31u) / 32u;
+    if ((uint64_t)r + L > n_rows) return set_err(MG_E_INVALID, "climb: coordinate rows past n_rows");
+  }
+  *res = mg_climb_res_t{};
+  res->first_hit = ~0ull;
+  res->best = ~0u;
+  const uint32_t burst = (uint32_t)std::min<uint64_t>({a->burst, kClimbBurstMax, a->rounds});
+
+  // the device block, in words: control | trajectory of one burst | hit rows || two row buffers |
+  // watch_row | coord_row | coord_has.  Everything before || is read back after every burst.
+  constexpr size_t kCtlWords = (sizeof(ClimbCtl) + 7) / 8 * 2;
+  const size_t o_traj = kCtlWords, o_hit = o_traj + (size_t)kClimbBurstMax * MG_SCORED_SLOTS * 2;
+  const size_t back_words = o_hit + ww + (ww & 1u);
+  const size_t rows_words = (size_t)n_rows * MG_SCORED_SLOTS;
+  const size_t o_rows = back_words, o_wrow = o_rows + 2 * rows_words, o_crow = o_wrow + n_rows, o_chas = o_crow + nc;
+  const size_t words = o_chas + nc;
+  if ((rc = ensure_scored(e, ww))) return rc;
+  if (words > e.climb_words) {
+    if (e.d_climb) (void)hipFree(e.d_climb);
+    if (e.h_climb) (void)hipHostFree(e.h_climb);
+    e.d_climb = e.h_climb = nullptr;
+    e.climb_words = 0;
+    HIPCHK(hipMalloc((void**)&e.d_climb, words * 4));
+    HIPCHK(hipHostMalloc((void**)&e.h_climb, words * 4, hipHostMallocDefault));
+    e.climb_words = words;
+  }
+  ClimbCtl* h_ctl = (ClimbCtl*)e.h_climb;
+  ClimbCtl* d_ctl = (ClimbCtl*)e.d_climb;
+  auto stopped = [&]() -> uint32_t {
+    if (a->cancel && *a->cancel) return MG_CLIMB_CANCEL;
+    if (a->budget_s &&
+        std::chrono::duration<double>(std::chrono::steady_clock::now() - t_entry).count() >= *a->budget_s)
+      return MG_CLIMB_BUDGET;
+    return 0u;
+  };
+  if ((res->stop = stopped())) return MG_OK;
+
+  // the start image: an empty population, and the row map with every mapped coordinate in every seed
+  std::memset(e.h_climb, 0, back_words * 4);
+  h_ctl->best = ~0u;
+  h_ctl->first_hit = ~0ull;
+  std::memcpy(e.h_climb + o_wrow, a->watch_row, (size_t)n_rows * 4);
+  std::memcpy(e.h_climb + o_crow, a->coord_row, (size_t)nc * 4);
+  for (uint32_t c = 0; c < nc; c++) e.h_climb[o_chas + c] = a->coord_row[c] == MG_NONE ? 0u : ~0u;
+  SeedArgs sd0{};
+  if ((rc = stage_seeds(e, *p, seeds, &sd0))) return rc;
+  HIPCHK(hipMemcpyAsync(e.d_climb, e.h_climb, back_words * 4, hipMemcpyHostToDevice, e.stream));
+  HIPCHK(hipMemcpyAsync(e.d_climb + o_wrow, e.h_climb + o_wrow, (words - o_wrow) * 4, hipMemcpyHostToDevice, e.stream));
+  if ((rc = arm_hits(e))) return rc;
+  constexpr size_t kSlotWords = (size_t)MG_SCORED_SLOTS * kSlotStride;
+  HIPCHK(hipMemcpyAsync(e.d_slots, e.h_slots, kSlotWords * sizeof(unsigned long long), hipMemcpyHostToDevice, e.stream));
+
+  uint32_t* d_rows[2] = {e.d_climb + o_rows, e.d_climb + o_rows + rows_words};
+  unsigned long long* d_traj = (unsigned long long*)(e.d_climb + o_traj);
+  const unsigned long long* h_traj = (const unsigned long long*)(e.h_climb + o_traj);
+  uint64_t queued = 0, ran = 0;
+  for (;;) {
+    const uint32_t nb = (uint32_t)std::min<uint64_t>(burst, a->rounds - queued);
+    HIPCHK(hipEventRecord(e.ev0, e.stream));
+    for (uint32_t j = 0; j < nb; j++) {
+      const uint64_t r = queued + j;
+      const SeedArgs sd = r ? SeedArgs{d_rows[(r - 1) & 1], e.d_climb + o_crow, e.d_climb + o_chas, 0u, a->keep16} : sd0;
+      const ClimbArgs cl{d_ctl, r ? 1u : 0u};
+      ScoreArgs sc{e.d_slots, 0u};
+      KArgs k{};
+      k.start = r * a->chunk;
+      k.seed = a->seed;
+      if ((rc = launch_seeded_async(e, *p, *dg, k, sd, a->chunk, &sc, &cl))) return rc;
+      sc.fetch = 1u;
+      k.watch = e.d_srows;
+      k.watch_words = ww;
+      if ((rc = launch_seeded_async(e, *p, *dg, k, sd, a->chunk, &sc, &cl))) return rc;
+      ClimbSel s{};
+      s.ctl = d_ctl;
+      s.slots = e.d_slots;
+      s.hit = e.d_hit;
+      s.srows = e.d_srows;
+      s.watch_row = e.d_climb + o_wrow;
+      s.prev_rows = d_rows[(r + 1) & 1];
+      s.new_rows = d_rows[r & 1];
+      s.traj = d_traj + (size_t)j * MG_SCORED_SLOTS;
+      s.hit_rows = e.d_climb + o_hit;
+      s.start = k.start;
+      s.ww = ww;
+      s.n_rows = n_rows;
+      s.beam = a->beam;
+      s.patience = a->patience;
+      s.rounds = (uint32_t)std::min<uint64_t>(a->rounds, 0xFFFFFFFFull);
+      s.cur = (uint32_t)(r & 1);
+      hipLaunchKernelGGL(k_climb_select, dim3(1), dim3(kWave), 0, e.stream, s);
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(e.ev1, e.stream));
+    HIPCHK(hipMemcpyAsync(e.h_climb, e.d_climb, back_words * 4, hipMemcpyDeviceToHost, e.stream));
+    HIPCHK(hipEventRecord(e.ev2, e.stream));
+    HIPCHK(hipEventSynchronize(e.ev2));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e.ev0, e.ev1));
+    queued += nb;
+    const uint64_t now_ran = h_ctl->rounds_run;
+    for (uint64_t r = ran; r < now_ran; r++)
+      for (uint32_t s = 0; s < MG_SCORED_SLOTS; s++) {
+        const unsigned long long wd = h_traj[(r - ran) * MG_SCORED_SLOTS + s];
+        if (traj_index) traj_index[r * MG_SCORED_SLOTS + s] = wd == ~0ull ? ~0ull : r * a->chunk + (wd & kSlotIndexMask);
+        if (traj_viol) traj_viol[r * MG_SCORED_SLOTS + s] = wd == ~0ull ? 0u : (uint32_t)(wd >> 48);
+      }
+    e.stats.launches += now_ran - ran;
+    e.stats.candidates += (now_ran - ran) * a->chunk;
+    e.stats.last_candidates = a->chunk;
+    e.stats.last_kernel_ms = ms;
+    e.stats.kernel_ms_total += ms;
+    if (burst_ms) burst_ms[res->n_bursts] = ms;
+    res->n_bursts++;
+    ran = now_ran;
+    if ((res->stop = h_ctl->done)) break;
+    if (queued >= a->rounds) {  // (the last round's step sets `done`; not reached)
+      res->stop = MG_CLIMB_ROUNDS;
+      break;
+    }
+    if ((res->stop = stopped())) break;
+  }
+  res->rounds_run = ran;
+  res->best = h_ctl->best;
+  res->first_hit = h_ctl->first_hit;
+  res->n_hits = h_ctl->n_hits;
+  res->n_pop = h_ctl->n_seeds;
+  e.stats.hits += h_ctl->n_hits;
+  for (uint32_t m = 0; m < res->n_pop; m++) {
+    res->pop_index[m] = h_ctl->pop_index[m];
+    res->pop_viol[m] = h_ctl->pop_viol[m];
+  }
+  if (res->stop == MG_CLIMB_HIT && assign_out) std::memcpy(assign_out, e.h_climb + o_hit, (size_t)ww * 4);
+  if (pop_rows && res->n_pop) {
+    const size_t n = (size_t)n_rows * res->n_pop;
+    HIPCHK(hipMemcpyAsync(e.h_climb + o_rows, d_rows[h_ctl->cur & 1u], n * 4, hipMemcpyDeviceToHost, e.stream));
+    HIPCHK(hipEventRecord(e.ev2, e.stream));
+    HIPCHK(hipEventSynchronize(e.ev2));
+    std::memcpy(pop_rows, e.h_climb + o_rows, n * 4);
+  }
+  return MG_OK;
+}
+
+int mg_climb_select_host(const uint64_t* slot_words, const uint32_t* srows, uint32_t watch_words,
+                         const uint32_t* watch_row, uint32_t n_rows, uint64_t start, uint32_t n_prev,
+                         const uint32_t* prev_viol, const uint64_t* prev_index, const uint32_t* prev_rows, uint32_t beam,
+                         uint32_t* n_out, uint32_t* out_viol, uint64_t* out_index, uint32_t* out_rows) {
+  if (!slot_words || !srows || !watch_row || !n_out || !out_viol || !out_index || !out_rows)
+    return set_err(MG_E_INVALID, "climb select: null argument");
+  if (n_prev > MG_SCORED_SLOTS || beam < 1u || beam > MG_SCORED_SLOTS || n_rows == 0)
+    return set_err(MG_E_INVALID, "climb select: n_prev or beam outside range, or no rows");
+  if (n_prev && (!prev_viol || !prev_index || !prev_rows)) return set_err(MG_E_INVALID, "climb select: null population");
+  for (uint32_t r = 0; r < n_rows; r++)
+    if (watch_row[r] >= watch_words) return set_err(MG_E_INVALID, "climb select: watch_row entry past watch_words");
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "slot words");
+  ClimbWork w;
+  const ClimbRows R{srows, watch_row, prev_rows, watch_words, n_prev};
+  mg_climb_select(R, (const unsigned long long*)slot_words, 1u, start, prev_viol, (const unsigned long long*)prev_index,
+                  n_rows, beam, w, out_rows);
+  *n_out = w.n_kept;
+  for (uint32_t m = 0; m < w.n_kept; m++) {
+    out_viol[m] = w.viol[w.kept[m]];
+    out_index[m] = w.index[w.kept[m]];
+  }
   return MG_OK;
 }
 

@@ -51,7 +51,7 @@ EXPORTS = [
     "mg_init", "mg_collective_kind", "mg_shutdown", "mg_last_error", "mg_version", "mg_program_check", "mg_program_check_gen",
     "mg_program_specialized", "mg_program_load",
     "mg_program_info", "mg_program_free", "mg_gen_load", "mg_gen_info", "mg_gen_free", "mg_eval", "mg_eval_dev",
-    "mg_eval_generated", "mg_search", "mg_search_batch", "mg_search_seeded", "mg_eval_seeded", "mg_search_scored", "mg_keccak256", "mg_stats", "mg_stats_reset", "mg_dev_alloc",
+    "mg_eval_generated", "mg_search", "mg_search_batch", "mg_search_seeded", "mg_eval_seeded", "mg_search_scored", "mg_search_climb", "mg_climb_select_host", "mg_keccak256", "mg_stats", "mg_stats_reset", "mg_dev_alloc",
     "mg_dev_free", "mg_dev_upload", "mg_dev_download", "mg_program_jit_source", "mg_program_jit_asm", "mg_code_object_check", "mg_jit_compile", "mg_jit_compile_ex", "mg_jit_verdicts", "mg_jit_info", "mg_jit_layout",
     "mg_jit_compile_async", "mg_jit_poll", "mg_jit_cancel", "mg_jit_helper_pid", "mg_cache_clear", "mg_split_range",
     "mg_jit_free", "mg_jit_search", "mg_jit_search_many", "mg_jit_eval", "mg_jit_eval_dev",
@@ -138,6 +138,55 @@ class ScoredRes(C.Structure):
     ]
 
 
+class ClimbArgsC(C.Structure):
+    """``mg_climb_args_t``."""
+    _fields_ = [
+        ("seeds", C.POINTER(SeedSetC)), ("coord_row", C.POINTER(C.c_uint32)), ("watch_row", C.POINTER(C.c_uint32)),
+        ("n_rows", C.c_uint32), ("keep16", C.c_uint32), ("seed", C.c_uint64), ("chunk", C.c_uint64),
+        ("rounds", C.c_uint64), ("beam", C.c_uint32), ("patience", C.c_uint32), ("burst", C.c_uint32),
+        ("reserved", C.c_uint32), ("cancel", C.POINTER(C.c_uint32)), ("budget_s", C.POINTER(C.c_double)),
+    ]
+
+
+class ClimbResC(C.Structure):
+    """``mg_climb_res_t``."""
+    _fields_ = [
+        ("first_hit", C.c_uint64), ("n_hits", C.c_uint64), ("rounds_run", C.c_uint64),
+        ("best", C.c_uint32), ("stop", C.c_uint32), ("n_pop", C.c_uint32), ("n_bursts", C.c_uint32),
+        ("pop_index", C.c_uint64 * MG_SCORED_SLOTS), ("pop_viol", C.c_uint32 * MG_SCORED_SLOTS),
+    ]
+
+
+CLIMB_STOP = {1: "hit", 2: "patience", 3: "rounds", 4: "rounds", 5: "cancel", 6: "budget"}
+
+
+class ClimbMap:
+    """The row map of a device climb (``mg_climb_args_t``): ``coord_row[c]`` is coordinate c's first
+    seed row (``MG_NONE``: never seeded), ``watch_row[r]`` the word of a candidate's watch rows that
+    seed row r is, ``keep16`` the keep probability of every round after the first."""
+
+    def __init__(self, coord_row, watch_row, keep16: int):
+        self.coord_row = np.ascontiguousarray(coord_row, dtype=np.uint32)
+        self.watch_row = np.ascontiguousarray(watch_row, dtype=np.uint32)
+        self.keep16 = int(keep16)
+
+    @property
+    def n_rows(self) -> int:
+        return int(self.watch_row.size)
+
+
+class DeviceClimb:
+    """What ``Engine.search_climb`` returns: ``index`` (None: no hit), ``hits``, ``assign`` (the hit's
+    watch rows), ``rounds``, ``best`` (None: no population yet), ``stop``, ``trajectory`` (per round
+    32 ``(index, violations)`` or None), ``population`` as ``[(violations, index)]`` with its seed
+    rows ``pop_rows`` ([n_rows][members]) and ``kernel_ms`` per burst."""
+
+    def __init__(self):
+        self.index, self.hits, self.assign, self.rounds, self.best, self.stop = None, 0, None, 0, None, None
+        self.trajectory, self.population, self.kernel_ms = [], [], []
+        self.pop_rows = None
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -190,6 +239,10 @@ def load_library(path: Optional[Path] = None) -> C.CDLL:
                                          C.c_uint64, u8p, u32p]),
             "mg_search_scored": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(SeedSetC), C.c_uint64, C.c_uint64,
                                            C.c_uint64, C.c_uint32, C.POINTER(ScoredRes), u32p]),
+            "mg_search_climb": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(ClimbArgsC), C.POINTER(ClimbResC), u32p,
+                                          u64p, u32p, u32p, C.POINTER(C.c_double)]),
+            "mg_climb_select_host": (C.c_int, [u64p, u32p, C.c_uint32, u32p, C.c_uint32, C.c_uint64, C.c_uint32, u32p,
+                                               u64p, u32p, C.c_uint32, u32p, u32p, u64p, u32p]),
             "mg_keccak256": (C.c_int, [u8p, u32p, C.c_uint64, u8p]),
             "mg_stats": (C.c_int, [C.POINTER(Stats)]),
             "mg_stats_reset": (C.c_int, []),
@@ -252,6 +305,36 @@ def _u8(buf: bytes):
 
 def _ptr(a: np.ndarray, ctype):
     return a.ctypes.data_as(C.POINTER(ctype))
+
+
+def climb_select_host(slot_words, srows, watch_row, start: int, prev_viol, prev_index, prev_rows, beam: int):
+    """One population step of the device climb on the host (``mg_climb_select_host``, the function
+    ``k_climb_select`` runs; no GPU).  ``slot_words``: 32 uint64 (``viol << 48 | i - start``, all
+    ones = empty), ``srows`` uint32[32][watch_words], ``prev_rows`` uint32[n_rows][n_prev].
+    Returns ``(viol list, index list, rows uint32[n_rows][n])``."""
+    lib = load_library()
+    slot_words = np.ascontiguousarray(slot_words, dtype=np.uint64)
+    srows = np.ascontiguousarray(srows, dtype=np.uint32)
+    watch_row = np.ascontiguousarray(watch_row, dtype=np.uint32)
+    prev_viol = np.ascontiguousarray(prev_viol, dtype=np.uint32)
+    prev_index = np.ascontiguousarray(prev_index, dtype=np.uint64)
+    prev_rows = np.ascontiguousarray(prev_rows, dtype=np.uint32)
+    if slot_words.size != MG_SCORED_SLOTS or srows.ndim != 2 or srows.shape[0] != MG_SCORED_SLOTS:
+        raise ValueError("climb_select_host: 32 slot words and 32 rows of watch words")
+    n_rows, n_prev = int(watch_row.size), int(prev_viol.size)
+    if prev_index.size != n_prev or prev_rows.size != n_rows * n_prev:
+        raise ValueError("climb_select_host: the previous population's arrays disagree")
+    n = C.c_uint32()
+    viol = np.zeros(MG_SCORED_SLOTS, dtype=np.uint32)
+    index = np.zeros(MG_SCORED_SLOTS, dtype=np.uint64)
+    rows = np.zeros(max(n_rows, 1) * MG_SCORED_SLOTS, dtype=np.uint32)
+    p = lambda a, t: _ptr(a, t) if a.size else None
+    _check(lib.mg_climb_select_host(_ptr(slot_words, C.c_uint64), p(srows, C.c_uint32), srows.shape[1],
+                                    p(watch_row, C.c_uint32), n_rows, start, n_prev, p(prev_viol, C.c_uint32),
+                                    p(prev_index, C.c_uint64), p(prev_rows, C.c_uint32), beam, C.byref(n),
+                                    _ptr(viol, C.c_uint32), _ptr(index, C.c_uint64), _ptr(rows, C.c_uint32)))
+    k = int(n.value)
+    return viol[:k].tolist(), index[:k].tolist(), rows[:n_rows * k].reshape(n_rows, k)
 
 
 def check_program(blob: bytes) -> ProgramInfo:
@@ -517,6 +600,57 @@ class Engine:
         _check(self.lib.mg_eval_seeded(prog, gen, C.byref(sc), seed, start, n, _ptr(ver, C.c_uint8),
                                        _ptr(watch, C.c_uint32) if watch is not None else None))
         return ver, watch
+
+    def search_climb(self, prog: int, gen: int, cmap: ClimbMap, seed: int, chunk: int, rounds: int = 16,
+                     beam: int = 8, patience: int = 4, burst: int = 8, seeds: Optional[SeedSet] = None,
+                     cancel=None, budget_s: Optional[float] = None) -> DeviceClimb:
+        """A whole climbing search in one call (``mg_search_climb``): the rounds of ``search.climb``
+        with the population step on the GPU, queued ``burst`` rounds at a time.  ``seeds`` is round
+        0's seed set (any layout), ``cmap`` the row map of the later rounds.  ``cancel``: a
+        ``threading.Event`` (read once, before the call) or a uint32 numpy word the engine reads
+        before every burst; ``budget_s``: seconds from now after which no further burst starts."""
+        ww = self.info(prog).watch_words
+        if not all(0 <= int(v) < (1 << b) for v, b in ((rounds, 64), (chunk, 64), (beam, 32), (patience, 32), (burst, 32))):
+            raise EngineError(MG_E_INVALID, "search_climb: argument out of range")
+        word = None
+        if isinstance(cancel, np.ndarray):
+            if cancel.dtype != np.uint32 or cancel.size < 1:
+                raise ValueError("search_climb: cancel must be a uint32 word")
+            word = cancel
+        elif cancel is not None:
+            word = np.array([1 if cancel.is_set() else 0], dtype=np.uint32)
+        n_rows = cmap.n_rows
+        valid = 0 < int(rounds) and int(rounds) * max(int(chunk), 1) <= (1 << 48)  # else the engine refuses: no buffers
+        cap = int(rounds) if valid else 1
+        assign = np.zeros(max(ww, 1), dtype=np.uint32)
+        traj_i = np.empty(cap * MG_SCORED_SLOTS, dtype=np.uint64)
+        traj_v = np.empty(cap * MG_SCORED_SLOTS, dtype=np.uint32)
+        pop_rows = np.zeros(max(n_rows, 1) * MG_SCORED_SLOTS, dtype=np.uint32)
+        ms = np.zeros(cap, dtype=np.float64)
+        sc = seeds.as_c() if seeds is not None else None
+        budget = C.c_double(budget_s) if budget_s is not None else None
+        p32 = lambda a: _ptr(a, C.c_uint32) if a.size else None
+        args = ClimbArgsC(C.pointer(sc) if sc is not None else None, p32(cmap.coord_row), p32(cmap.watch_row),
+                          n_rows, cmap.keep16, seed, chunk, rounds, beam, patience, burst, 0,
+                          _ptr(word, C.c_uint32) if word is not None else None,
+                          C.pointer(budget) if budget is not None else None)
+        res = ClimbResC()
+        _check(self.lib.mg_search_climb(prog, gen, C.byref(args), C.byref(res), _ptr(assign, C.c_uint32),
+                                        _ptr(traj_i, C.c_uint64), _ptr(traj_v, C.c_uint32), _ptr(pop_rows, C.c_uint32),
+                                        _ptr(ms, C.c_double)))
+        out = DeviceClimb()
+        out.rounds, out.stop = int(res.rounds_run), CLIMB_STOP[int(res.stop)]
+        out.best = None if res.best == MG_NONE else int(res.best)
+        if res.first_hit != NO_HIT:
+            out.index, out.hits, out.assign = int(res.first_hit), int(res.n_hits), assign[:max(ww, 1)]
+        ti, tv = traj_i[:out.rounds * MG_SCORED_SLOTS].tolist(), traj_v[:out.rounds * MG_SCORED_SLOTS].tolist()
+        out.trajectory = [[None if ti[q] == NO_HIT else (ti[q], tv[q]) for q in range(r * MG_SCORED_SLOTS, (r + 1) * MG_SCORED_SLOTS)]
+                          for r in range(out.rounds)]
+        n_pop = int(res.n_pop)
+        out.population = [(int(res.pop_viol[m]), int(res.pop_index[m])) for m in range(n_pop)]
+        out.pop_rows = pop_rows[:n_rows * n_pop].reshape(n_rows, n_pop) if n_pop else np.zeros((n_rows, 0), dtype=np.uint32)
+        out.kernel_ms = ms[:int(res.n_bursts)].tolist()
+        return out
 
     # JIT-specialised kernels --------------------------------------
     def jit_compile(self, prog: int, gen: int = 0, gen_verdicts: bool = False, asm: bool = False,

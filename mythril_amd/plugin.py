@@ -442,11 +442,14 @@ def _climb_kw() -> dict:
     """``{"climb": ClimbConfig()}`` for ``search_partitioned`` under ``MYTHGPU_CLIMB=1`` (default off:
     {} and the call is what it was): a search whose first launch missed runs one climbing search
     on violation counts (``search.climb``) before it goes on sampling.  A model found that way is
-    re-checked by z3 like any other."""
+    re-checked by z3 like any other.  ``MYTHGPU_CLIMB_DEVICE=1`` (only together with it) runs the
+    climb's rounds on the GPU: ``ClimbConfig(device=True)``."""
     if os.environ.get("MYTHGPU_CLIMB", "0") != "1":
         return {}
     from .search import ClimbConfig
 
+    if os.environ.get("MYTHGPU_CLIMB_DEVICE", "0") == "1":
+        return {"climb": ClimbConfig(device=True)}
     return {"climb": ClimbConfig()}
 
 

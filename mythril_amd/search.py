@@ -540,12 +540,17 @@ def warm_keep16(n_eligible: int) -> int:
 class ClimbConfig:
     """The climbing search's limits: at most ``rounds`` scored sweeps, a population of at most
     ``beam`` assignments (the engine takes up to 32 seeds), and ``patience`` rounds in a row that do
-    not lower the best violation count before it gives up."""
+    not lower the best violation count before it gives up.  ``device``: run the rounds on the GPU
+    (``mg_search_climb``: the population step is a kernel and ``burst`` rounds are queued per host
+    wait) when the engine can; the search is the same, round for round."""
 
-    def __init__(self, rounds: int = 16, beam: int = 8, patience: int = 4):
+    def __init__(self, rounds: int = 16, beam: int = 8, patience: int = 4, device: bool = False, burst: int = 8):
         if not (rounds >= 1 and 1 <= beam <= 32 and patience >= 1):
             raise ValueError("ClimbConfig: rounds >= 1, 1 <= beam <= 32, patience >= 1")
+        if not burst >= 1:
+            raise ValueError("ClimbConfig: burst >= 1")
         self.rounds, self.beam, self.patience = int(rounds), int(beam), int(patience)
+        self.device, self.burst = bool(device), int(burst)
 
 
 class ClimbResult:
@@ -554,7 +559,8 @@ class ClimbResult:
     all); ``best`` is the lowest violation count seen; ``trajectory[r]`` the 32 slots of round r as
     ``engine.search_scored`` returned them; ``population`` the last population as
     ``(violations, index, {coordinate: value})``; ``stop`` why it ended ("hit", "rounds",
-    "patience", "cancel", "budget"); ``kernel_ms[r]`` the engine's kernel time of round r's sweep."""
+    "patience", "cancel", "budget"); ``kernel_ms[r]`` the engine's kernel time of round r's sweep
+    (the device path: of burst r, all its launches)."""
 
     def __init__(self):
         self.index = None
@@ -610,6 +616,60 @@ def next_population(previous: Sequence[tuple], winners: Sequence[tuple], beam: i
     return out
 
 
+def climb_map(P: ssa.Program):
+    """The row map of a device climb (``native.ClimbMap``, built once per Program): the layout
+    ``population_seeds`` gives a population of ``coords_from_assignment`` models — the scalars, the
+    AUX words in use and the base value of every non-LAZY site that has one, in coordinate order —
+    with, per seed row, the word of the model watch rows it is (``_model_plan``).  None when there is
+    nothing to seed or a watch entry's width is not its coordinate's (the host loop handles those)."""
+    from .native import ClimbMap
+
+    cm = getattr(P, "_climb_map", None)
+    if cm is not None:
+        return cm or None
+    _, widths, (scal, aux, sites) = _model_layout(P)
+    plan = _model_plan(P)
+    pos = {c.index: p for (p, _), c in zip(scal, P.scalar_coords())}
+    pos.update(aux)
+    pos.update({c.index: bpos for c, (_, _, _, _, bpos, _) in zip(P.sites, sites)
+                if bpos is not None and not _is_lazy(P, c)})
+    coord_row = np.full(len(P.coords), NONE, dtype=np.uint32)
+    watch_row: List[int] = []
+    ok = True
+    for c in P.coords:
+        p = pos.get(c.index)
+        if p is None or _is_lazy(P, c):
+            continue
+        ok = ok and widths[p] == c.width
+        coord_row[c.index] = len(watch_row)
+        watch_row += [plan[p][0] // 4 + j for j in range(ssa.limbs(c.width))]
+    cm = ClimbMap(coord_row, watch_row, warm_keep16(int((coord_row != NONE).sum()))) if ok and watch_row else False
+    P._climb_map = cm
+    return cm or None
+
+
+def _climb_device(engine, P: ssa.Program, prog: int, gh: int, seed: int, chunk: int, cfg: ClimbConfig, cmap,
+                  cancel, seeds, deadline: Optional[float]) -> ClimbResult:
+    """``climb`` through ``engine.search_climb``: one call, the same ``ClimbResult``."""
+    budget = None if deadline is None else deadline - time.perf_counter()
+    dc = engine.search_climb(prog, gh, cmap, seed, chunk, rounds=cfg.rounds, beam=cfg.beam, patience=cfg.patience,
+                             burst=cfg.burst, seeds=seeds, cancel=cancel, budget_s=budget)
+    out = ClimbResult()
+    out.rounds, out.candidates, out.best, out.stop = dc.rounds, dc.rounds * chunk, dc.best, dc.stop
+    out.trajectory, out.kernel_ms = dc.trajectory, list(dc.kernel_ms)
+    if dc.index is not None:
+        out.index, out.hits, out.assign = dc.index, dc.hits, np.array(dc.assign, dtype=np.uint32)
+    rows = np.asarray(dc.pop_rows)
+    for m, (v, i) in enumerate(dc.population):
+        model = {}
+        for c in P.coords:
+            r = int(cmap.coord_row[c.index])
+            if r != NONE:
+                model[c.index] = ssa.limbs_to_int(rows[r:r + ssa.limbs(c.width), m])
+        out.population.append((v, i, model))
+    return out
+
+
 def climb(engine, P: ssa.Program, prog: int, gh: int, seed: int, chunk: int, cfg: Optional[ClimbConfig] = None,
           cancel=None, seeds=None, deadline: Optional[float] = None) -> ClimbResult:
     """Stochastic local search on violation counts (``mg_search_scored``).  Round r sweeps
@@ -617,8 +677,17 @@ def climb(engine, P: ssa.Program, prog: int, gh: int, seed: int, chunk: int, cfg
     a ``native.SeedSet``, e.g. ``ModelCache.lookup``), every later round seeded from the population
     (``population_seeds``), which ``next_population`` rebuilds from each round's 32 slot winners.
     It stops at a hit, after ``cfg.rounds`` rounds, after ``cfg.patience`` rounds without a lower
-    best, when ``cancel`` is set or ``deadline`` (a ``time.perf_counter`` value) has passed."""
+    best, when ``cancel`` is set or ``deadline`` (a ``time.perf_counter`` value) has passed.
+
+    With ``cfg.device`` and an engine that has ``search_climb`` the same climb runs in one engine call
+    (``_climb_device``; ``cancel`` and ``deadline`` are then looked at per burst of ``cfg.burst``
+    rounds, ``kernel_ms`` is per burst); a program without a row map (``climb_map``) takes the loop
+    below."""
     cfg = cfg or ClimbConfig()
+    if cfg.device and hasattr(engine, "search_climb"):
+        cmap = climb_map(P)
+        if cmap is not None:
+            return _climb_device(engine, P, prog, gh, seed, chunk, cfg, cmap, cancel, seeds, deadline)
     out = ClimbResult()
     population: List[tuple] = []
     stale = 0

@@ -17,7 +17,12 @@ What must hold (exit status 1 otherwise): every stream query answered sat with c
 answered sat with climb on, with the same counts in every repeat.  No threshold is set on the
 times or on the families.
 
-usage: python tools/climb_bench.py [--repeats 5] [--workloads a,b] [--out profiles/climb_stream.json]
+``--device``: the same streams and conjunctions (and the chain's long climb) with the host climb
+against the device climb (``ClimbConfig(device=True)``, ``mg_search_climb``), alternating in one
+process: wall time per climb round, time to first model and kernel time per round for each path,
+to ``profiles/climb_device.json``.  Exit status 1 when the two paths do not run the same search.
+
+usage: python tools/climb_bench.py [--repeats 5] [--workloads a,b] [--out profiles/climb_stream.json] [--device]
 """
 import argparse
 import json
@@ -59,7 +64,8 @@ def run_stream(eng, queries, cfg, max_candidates, timeout_s):
         tm = r.timing if "climb_rounds" in r.timing else last
         rounds = tm.get("climb_rounds", 0)
         out.append((r.index is not None, rounds > 0, "climb" in str(getattr(r, "engine", "")),
-                    r.scanned + tm.get("climb_candidates", 0), ms, rounds, list(tm.get("climb_kernel_ms", []))))
+                    r.scanned + tm.get("climb_candidates", 0), ms, rounds, list(tm.get("climb_kernel_ms", [])),
+                    tm.get("climb_ms", 0.0)))
     return out
 
 
@@ -117,8 +123,110 @@ def chain_stall(eng, roots, rounds, chunk=4096):
     return out
 
 
+PATHS = (("host", False), ("device", True))
+
+
+def per_round(passes):
+    """Wall and kernel time per climb round over the queries on which the climb ran: the climb's
+    time (``timing["climb_ms"]``) and its kernels' (per round on the host path, per burst on the
+    device path) over its rounds."""
+    ran = [q for p in passes for q in p if q[5]]
+    rounds = sum(q[5] for q in ran)
+    return {"round_wall_ms": r3(sum(q[7] for q in ran) / rounds) if rounds else None,
+            "round_kernel_ms": r3(sum(sum(q[6]) for q in ran) / rounds) if rounds else None,
+            "climb_ms_p50": r3(pct([q[7] for q in ran], 0.5))}
+
+
+def device_streams(eng, names, a):
+    rows = []
+    for name in names:
+        qs = stream_queries(name)
+        cfgs = {p: search.ClimbConfig(device=d) for p, d in PATHS}
+        run = lambda c: run_stream(eng, qs, c, a.max_candidates, a.timeout_s)
+        for c in cfgs.values():
+            run(c)  # untimed
+        passes = {p: [] for p in cfgs}
+        for _ in range(a.repeats):
+            for p, c in cfgs.items():
+                passes[p].append(run(c))
+        row = {"workload": name, "max_candidates": a.max_candidates, "repeats": a.repeats}
+        for p in cfgs:
+            row[p] = dict(summarize(passes[p]), **per_round(passes[p]))
+        # the same search: the same answers, rounds and candidates query by query
+        row["same_counts"] = [q[:4] + (q[5],) for q in passes["host"][0]] == [q[:4] + (q[5],) for q in passes["device"][0]]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
+def device_family(eng, label, roots, cfg_kw, a, repeats=3, chunk=4096):
+    """Host climb against device climb on one query through ``search.search``, per seed: time to the
+    first model (the ordinary first launch included), the climb's wall time per round and its kernel
+    time per round; the paths alternate, after one untimed run of each."""
+    runs = []
+    for seed in SEEDS:
+        row = {"seed": seed}
+        for p, d in PATHS:
+            row[p] = {"ms": [], "climb_ms": [], "kernel_ms": []}
+        for rep in range(repeats + 1):
+            for p, d in PATHS:
+                cfg = search.ClimbConfig(device=d, **cfg_kw)
+                t = time.perf_counter()
+                # one ordinary launch, the climb, and after a climb that missed one ordinary launch more
+                r = search.search(eng, roots, seed=seed, chunk=chunk, max_candidates=2 * chunk, timeout_s=a.timeout_s,
+                                  jit="never", climb=cfg)
+                ms = (time.perf_counter() - t) * 1e3
+                x = row[p]
+                x.update({"sat": r.index is not None, "index": r.index, "rounds": r.timing.get("climb_rounds"),
+                          "best_violations": r.timing.get("climb_best")})
+                if rep:
+                    x["ms"].append(ms)
+                    x["climb_ms"].append(r.timing.get("climb_ms", 0.0))
+                    x["kernel_ms"].append(sum(r.timing.get("climb_kernel_ms", [])))
+        for p, _ in PATHS:
+            x = row[p]
+            x["ms"], x["climb_ms"], x["kernel_ms"] = (r3(pct(x[k], 0.5)) for k in ("ms", "climb_ms", "kernel_ms"))
+        row["same_search"] = all(row["host"][k] == row["device"][k] for k in ("sat", "index", "rounds", "best_violations"))
+        runs.append(row)
+    out = {"query": label, "roots": len(roots), "config": cfg_kw or "default", "chunk": chunk, "runs": runs,
+           "same_search": all(x["same_search"] for x in runs)}
+    for p, _ in PATHS:
+        xs = [x[p] for x in runs]
+        sat = [x for x in xs if x["sat"]]
+        rounds = sum(x["rounds"] or 0 for x in xs)
+        out[p] = {"sat": len(sat), "of": len(xs), "rounds_min": min(x["rounds"] for x in xs), "rounds_max": max(x["rounds"] for x in xs),
+                  "first_model_ms_p50": r3(pct([x["ms"] for x in sat], 0.5)), "ms_p50": r3(pct([x["ms"] for x in xs], 0.5)),
+                  "round_wall_ms": r3(sum(x["climb_ms"] for x in xs) / rounds) if rounds else None,
+                  "round_kernel_ms": r3(sum(x["kernel_ms"] for x in xs) / rounds) if rounds else None}
+    print(json.dumps({k: v for k, v in out.items() if k != "runs"}), flush=True)
+    return out
+
+
+def main_device(a, eng):
+    """``--device``: everything above again, host climb against device climb in one process."""
+    names = [w for w in a.workloads.split(",") if w]
+    doc = {"tool": "tools/climb_bench.py --device", "device": f"gfx950 ({eng.stats().cu_count} CUs)",
+           "config": {"rounds": 16, "beam": 8, "patience": 4, "chunk": 4096, "burst": 8},
+           "streams": device_streams(eng, names, a), "families": [], "chain_long": None}
+    for n in (4, 6, 8, 10):
+        doc["families"].append(device_family(eng, f"star{n}", workloads.climb_star(n, f"st{n}"), {}, a))
+    chain = workloads.climb_chain(8)
+    doc["families"].append(device_family(eng, "chain8", chain, {}, a))
+    doc["chain_long"] = device_family(eng, "chain8", chain, {"rounds": a.chain_rounds, "patience": a.chain_rounds}, a)
+    out = a.out if a.out != str(ROOT / "profiles" / "climb_stream.json") else str(ROOT / "profiles" / "climb_device.json")
+    Path(out).parent.mkdir(parents=True, exist_ok=True)
+    Path(out).write_text(json.dumps(doc, indent=1) + "\n")
+    differ = [r["workload"] for r in doc["streams"] if not r["same_counts"]]
+    differ += [f["query"] for f in doc["families"] + [doc["chain_long"]] if not f["same_search"]]
+    if differ:
+        print("host and device climb differ on:", ", ".join(differ), file=sys.stderr)
+    return 1 if differ else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--device", action="store_true",
+                    help="host climb against device climb (ClimbConfig(device=True)); writes profiles/climb_device.json")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--workloads", default=",".join(workloads.WORKLOADS))
     ap.add_argument("--max-candidates", type=int, default=1 << 22)
@@ -128,6 +236,8 @@ def main():
     ap.add_argument("--out", default=str(ROOT / "profiles" / "climb_stream.json"))
     a = ap.parse_args()
     eng = native.Engine.get()
+    if a.device:
+        return main_device(a, eng)
     cfg = search.ClimbConfig()
     rows, lost, unstable = [], [], []
     t0 = time.perf_counter()
