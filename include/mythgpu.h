@@ -143,7 +143,13 @@ enum mg_table_kind { MG_TABLE_ARRAY = 0, MG_TABLE_UF = 1 };
  *   group key   G = fmix64((i >> 6) ^ fmix64(seed ^ 0xBB67AE8584CAA73B)) (G_lo, G_hi)
  *   lane key    K = G ^ fmix64((i & 63) ^ fmix64(seed ^ 0x6A09E667F3BCC908))  (K_lo, K_hi)
  * G is a bijection of the group number and K of the lane within a group, so the
- * pair (G, K) is distinct for every index (all 2^64 indices are usable).  G is
+ * pair (G, K) is distinct for every index.  WINDOWS: every call that sweeps candidates
+ * [start, start + count) requires count <= UINT64_MAX - start, so candidate indices are
+ * 0 .. 2^64 - 2 (index 2^64 - 1 is the "no hit" value of first_hit, and the kernels test
+ * idx < start + count, which must not wrap).  mg_search, mg_search_batch (every entry),
+ * mg_eval_generated, mg_search_seeded, mg_eval_seeded, mg_search_scored, mg_jit_search,
+ * mg_jit_search_many (every launch), mg_jit_verdicts and mg_split_range return MG_E_INVALID
+ * for any other window, before anything is queued (mg_search_climb bounds rounds * chunk).  G is
  * shared by the 64 consecutive indices of one aligned group — exactly one wave of
  * the search kernels — so a choice made from G is wave-uniform (a scalar branch,
  * not a per-lane select); the lane half of K is a per-thread constant.

@@ -1482,6 +1482,15 @@ static int set_err(int code, const std::string& m) {
   return code;
 }
 
+// A window [start, start + count) must satisfy count <= UINT64_MAX - start (include/mythgpu.h,
+// "windows"): every kernel tests idx < start + count, and an end that wraps to 0 masks off every
+// lane, so such a sweep would report no hit with MG_OK.  Checked before anything is queued.
+static int check_window(const char* who, uint64_t start, uint64_t count) {
+  if (count > UINT64_MAX - start)
+    return set_err(MG_E_INVALID, std::string(who) + ": window reaches 2^64 (count > UINT64_MAX - start)");
+  return MG_OK;
+}
+
 template <class T>
 static int upload(T** d, const T* h, size_t n) {
   *d = nullptr;
@@ -2131,13 +2140,16 @@ int mg_init(uint32_t device_mask) {
 
 int mg_split_range(uint64_t start, uint64_t count, uint32_t n_dev, uint64_t* starts, uint64_t* counts) {
   if (n_dev == 0 || !starts || !counts) return set_err(MG_E_INVALID, "mg_split_range: bad arguments");
+  if (int rc = check_window("mg_split_range", start, count)) return rc;
   // whole aligned 64-index groups per device (one group = one wave, GEN3 group key), in
   // index order: device d scans the d-th contiguous slice
   const uint64_t end = start + count, a0 = start & ~63ull;
   const uint64_t ngroups = count ? (end - a0 + 63ull) >> 6 : 0;
   for (uint32_t d = 0; d < n_dev; d++) {
     const uint64_t g0 = ngroups * d / n_dev, g1 = ngroups * (d + 1) / n_dev;
-    const uint64_t lo = std::max<uint64_t>(start, a0 + 64ull * g0), hi = std::min<uint64_t>(end, a0 + 64ull * g1);
+    // (the last slice ends at `end`: a0 + 64 g1 is 2^64, which wraps, when the window's last group is the top one)
+    const uint64_t lo = std::max<uint64_t>(start, a0 + 64ull * g0);
+    const uint64_t hi = g1 == ngroups ? end : std::min<uint64_t>(end, a0 + 64ull * g1);
     starts[d] = lo;
     counts[d] = hi > lo ? hi - lo : 0;
   }
@@ -2588,6 +2600,7 @@ int mg_eval_generated(uint64_t prog, uint64_t gen, uint64_t seed, uint64_t start
   if (!p) return set_err(MG_E_INVALID, "bad program handle");
   auto it = e.gens.find(gen);
   if (it == e.gens.end() || it->second->prog != prog) return set_err(MG_E_INVALID, "bad generator handle");
+  if (int rc = check_window("mg_eval_generated", start, n)) return rc;
   if (n == 0) return MG_OK;
   const size_t watch_bytes = (size_t)p->low.watch_words * n * 4;
   uint32_t* d_watch = nullptr;
@@ -2682,6 +2695,7 @@ static int search_locked(Engine& e, uint64_t prog, uint64_t gen, uint64_t seed, 
   if (!p) return set_err(MG_E_INVALID, "bad program handle");
   auto it = e.gens.find(gen);
   if (it == e.gens.end() || it->second->prog != prog) return set_err(MG_E_INVALID, "bad generator handle");
+  if (int rc = check_window("mg_search", start, count)) return rc;
   unsigned long long res[2] = {~0ull, 0ull};
   if (split_over_devices(count)) {
     // the node's devices each sweep one contiguous, group-aligned slice (mg_split_range) on
@@ -2942,6 +2956,7 @@ int mg_search_seeded(uint64_t prog, uint64_t gen, const mg_seed_set_t* seeds, ui
   DevGen* dg;
   int rc = check_seeded(e, prog, gen, seeds, &p, &dg);
   if (rc) return rc;
+  if ((rc = check_window("mg_search_seeded", start, count))) return rc;
   unsigned long long res[2] = {~0ull, 0ull};
   SeedArgs sd{};
   if (count) {
@@ -2984,6 +2999,7 @@ int mg_eval_seeded(uint64_t prog, uint64_t gen, const mg_seed_set_t* seeds, uint
   DevGen* dg;
   int rc = check_seeded(e, prog, gen, seeds, &p, &dg);
   if (rc) return rc;
+  if ((rc = check_window("mg_eval_seeded", start, n))) return rc;
   if (n && !verdict_out) return set_err(MG_E_INVALID, "verdict_out: null");
   if (n == 0) return MG_OK;
   const size_t watch_bytes = (size_t)p->low.watch_words * n * 4;
@@ -3048,6 +3064,7 @@ int mg_search_scored(uint64_t prog, uint64_t gen, const mg_seed_set_t* seeds, ui
   if (rc) return rc;
   if (!res) return set_err(MG_E_INVALID, "res: null");
   if (count > (1ull << 48)) return set_err(MG_E_INVALID, "count above 2^48");
+  if ((rc = check_window("mg_search_scored", start, count))) return rc;
   // a violation count is 16 bits of the slot word: one assert per distinct root node
   size_t n_asserts = 0;
   for (const Instr& in : p->low.code) n_asserts += in.op == K_ASSERT || in.op == K_ASSERT_CMP;
@@ -3476,6 +3493,7 @@ int mg_search_batch(uint32_t n, const mg_search_req_t* reqs, uint32_t flags, mg_
     if (!find_prog(e, reqs[q].prog)) return set_err(MG_E_INVALID, "mg_search_batch: bad program handle in entry " + std::to_string(q));
     if (it == e.gens.end() || it->second->prog != reqs[q].prog)
       return set_err(MG_E_INVALID, "mg_search_batch: bad generator handle in entry " + std::to_string(q));
+    if (int rc = check_window(("mg_search_batch: entry " + std::to_string(q)).c_str(), reqs[q].start, reqs[q].count)) return rc;
   }
   std::vector<uint32_t> in_batch, alone;
   for (uint32_t q = 0; q < n; q++) {
@@ -4193,6 +4211,7 @@ int mg_jit_search(uint64_t jit, uint64_t seed, uint64_t start, uint64_t count, u
   if (!p || git == e.gens.end() || !j.fsearch) return set_err(MG_E_INVALID, "jit was not compiled for search");
   // the search kernel counts each wave's groups in 32 bits (jit.cpp): at most 2^52 candidates per call
   if (count > (1ull << 52)) return set_err(MG_E_INVALID, "mg_jit_search: more than 2^52 candidates in one call");
+  if (int rc = check_window("mg_jit_search", start, count)) return rc;
   uint64_t sk = seed_lane_key(seed), sg = seed_group_key(seed);
   unsigned long long res[2] = {~0ull, 0ull};
   if (split_over_devices(count)) {  // as mg_search: one group-aligned slice per device, host min/sum
@@ -4265,6 +4284,8 @@ int mg_jit_search_many(uint64_t jit, uint32_t n, const uint64_t* seeds, const ui
                        uint32_t flags, uint64_t* first_hits, uint64_t* n_hits) {
   if (n == 0) return MG_OK;
   if (!seeds || !starts || !counts || !first_hits || !n_hits) return set_err(MG_E_INVALID, "mg_jit_search_many: null array");
+  for (uint32_t q = 0; q < n; q++)  // before anything is queued, on the split path too
+    if (int rc = check_window(("mg_jit_search_many: launch " + std::to_string(q)).c_str(), starts[q], counts[q])) return rc;
   Engine& e = E();
   bool split = false;
   for (uint32_t q = 0; q < n; q++) split = split || split_over_devices(counts[q]);
@@ -4349,6 +4370,7 @@ int mg_jit_verdicts(uint64_t jit, uint64_t seed, uint64_t start, uint64_t n, uin
   DevJit& j = *it->second;
   auto git = e.gens.find(j.gen);
   if (git == e.gens.end() || !j.fgen) return set_err(MG_E_INVALID, "jit was not compiled with MG_JIT_GEN_VERDICTS");
+  if (int rc = check_window("mg_jit_verdicts", start, n)) return rc;
   if (n == 0) return MG_OK;
   uint8_t* d_ver = nullptr;
   HIPCHK(hipMalloc((void**)&d_ver, n));

@@ -106,8 +106,10 @@ class GenBuilder:
         w = self.P.coords[c].width
         values = list(values)
         off = self._push(values, w) if values else 0
-        pc = int(p_copy * P16) if copy_from is not None else 0
-        pd = int(p_dict * P16) if values else 0
+        # 16-bit fixed point saturates: p = 1.0 is 65535/65536, not 65536 & 0xFFFF = never
+        p16 = lambda p: max(0, min(int(p * P16), P16 - 1))  # noqa: E731
+        pc = p16(p_copy) if copy_from is not None else 0
+        pd = p16(p_dict) if values else 0
         rec = 0
         if clamp is not None:
             lo, span = clamp
@@ -115,9 +117,9 @@ class GenBuilder:
             self.consts.extend(ssa.int_to_limbs(lo % (1 << w), w))
             self.consts.append(span & 0xFFFFFFFF)
         self.specs[c] = [
-            GEN_MIXED, off, len(values), (pc & 0xFFFF) | ((pd & 0xFFFF) << 16),
+            GEN_MIXED, off, len(values), pc | (pd << 16),
             NONE if copy_from is None else copy_from,
-            (int(p_small * P16) & 0xFFFF) | ((small_bits & 0xFFFF) << 16), int(p_delta * P16) & 0xFFFF, rec,
+            p16(p_small) | ((small_bits & 0xFFFF) << 16), p16(p_delta), rec,
         ]
 
     def fix(self, c: int, mask: int, value: int):

@@ -7,36 +7,12 @@ import numpy as np
 
 from mythril_amd import ssa
 from oracle import cport
+from tests.gen3_ref import fmix64, lane_key, rnd_at as rnd  # noqa: F401
 
 M64 = (1 << 64) - 1
 M32 = 0xFFFFFFFF
 GEN_LAZY = 6
 NONE = 0xFFFFFFFF
-
-
-def fmix64(x: int) -> int:
-    x ^= x >> 33
-    x = (x * 0xFF51AFD7ED558CCD) & M64
-    x ^= x >> 33
-    x = (x * 0xC4CEB9FE1A85EC53) & M64
-    x ^= x >> 33
-    return x
-
-
-def lane_key(seed: int, i: int) -> int:
-    """K of candidate i (GEN3)."""
-    g = fmix64((i >> 6) ^ fmix64(seed ^ 0xBB67AE8584CAA73B))
-    return g ^ fmix64((i & 63) ^ fmix64(seed ^ 0x6A09E667F3BCC908))
-
-
-def rnd(seed: int, i: int, c: int, j: int) -> int:
-    """GEN3's rnd(c, j) = fin(K_lo ^ salt(c, j)) + K_hi of candidate i."""
-    k = lane_key(seed, i)
-    x = (k & M32) ^ ((c * 0x9E3779B9 + j * 0x85EBCA6B + 0x27D4EB2F) & M32)
-    x ^= x >> 16
-    x = ((x & 0xFFFFFF) * 0x9E3779) & M32
-    x ^= x >> 15
-    return (x + (k >> 32)) & M32
 
 
 def lazy_coords(gen_blob) -> set:

@@ -11,57 +11,7 @@ import pytest
 from mythril_amd import search, ssa
 from mythril_amd.smt import symbol_factory
 from oracle import cport
-
-M32, M64 = (1 << 32) - 1, (1 << 64) - 1
-
-
-def fmix64(x):
-    x ^= x >> 33
-    x = (x * 0xFF51AFD7ED558CCD) & M64
-    x ^= x >> 33
-    x = (x * 0xC4CEB9FE1A85EC53) & M64
-    x ^= x >> 33
-    return x
-
-
-def keys(idx, seed):
-    G = fmix64((idx >> 6) ^ fmix64(seed ^ 0xBB67AE8584CAA73B))
-    K = G ^ fmix64((idx & 63) ^ fmix64(seed ^ 0x6A09E667F3BCC908))
-    return K & M32, K >> 32, G & M32, G >> 32
-
-
-def salt(c, j):
-    return (c * 0x9E3779B9 + j * 0x85EBCA6B + 0x27D4EB2F) & M32
-
-
-def fin(x):
-    x ^= x >> 16
-    x = ((x & 0xFFFFFF) * 0x9E3779) & M32
-    x ^= x >> 15
-    return x
-
-
-def rnd(k, c, j):
-    return (fin(k[0] ^ salt(c, j)) + k[1]) & M32
-
-
-def wsel(k, c):
-    return ((k[2] ^ salt(c, 0xFFFE)) * 0x9E3779B1 + k[3]) & M32
-
-
-def uniform_raw(k, c, L):
-    u = []
-    for j in range(L):
-        if j < 2:
-            u.append(rnd(k, c, j))
-        else:
-            s = (7 * j + 3) % 31 + 1
-            u.append(((((u[j - 1] << 32) | u[j - 2]) >> s) + u[j - 2]) & M32)
-    return u
-
-
-def value(limbs, w):
-    return sum(x << (32 * j) for j, x in enumerate(limbs)) & ((1 << w) - 1)
+from tests.gen3_ref import keys, rnd, uniform_raw, value, wsel  # noqa: F401  (imported from here by other tests)
 
 
 def one_query(w, v, spec):
