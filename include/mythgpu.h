@@ -183,6 +183,10 @@ enum mg_table_kind { MG_TABLE_ARRAY = 0, MG_TABLE_UF = 1 };
  *              lo <= v < lo + span, else v = lo + (((u64)limb0(v) * span) >> 32)
  *              (span 0 = 2^32; lo + span <= 2^w is checked at load).
  * Finally every kind applies its fixed-bit record (kind bits 8..31).
+ * Constants may carry bits the generator does not use: a FIXED value and a DICT / MIXED
+ * dictionary entry are read masked to w, and a fix record's value is ORed in whole, also
+ * where its mask is 0 (v = (v & ~mask) | value), so such a bit is always 1; a value with
+ * a bit at or above w is refused at load (MG_E_INVALID).
  * Probabilities are 16-bit fixed point (/65536).
  */
 #define MG_GEN_MAGIC 0x334E4547u /* "GEN3" */

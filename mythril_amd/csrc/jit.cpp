@@ -674,12 +674,13 @@ struct Gen {
     }
     if (width & 31) o << "  " << lim(L - 1) << " &= " << hex(topmask(width)) << ";\n";
     if (fix) {
-      // fixed bits are literals here: (v & ~mask) | value
+      // fixed bits are literals here: (v & ~mask) | value; the value's bits count outside the mask too
       const uint32_t f = fix - 1;
       for (uint32_t j = 0; j < L; j++) {
         const uint32_t m = G[f + j], val = G[f + L + j];
         if (m == 0xFFFFFFFFu) o << "  " << lim(j) << " = " << hex(val) << ";\n";
         else if (m) o << "  " << lim(j) << " = (" << lim(j) << " & " << hex(~m) << ") | " << hex(val) << ";\n";
+        else if (val) o << "  " << lim(j) << " |= " << hex(val) << ";\n";
       }
     }
     o << "  }\n";

@@ -2955,13 +2955,13 @@ struct Gen {
     const uint32_t f = fix - 1, Lc = (uint32_t)r.size();
     for (uint32_t j = 0; j < Lc; j++) {
       const uint32_t m = G[f + j], v = G[f + Lc + j];
-      if (!m) continue;
+      if (!m && !v) continue;  // (the value's bits count outside the mask too)
       if (in_place) {
         if (m == 0xFFFFFFFFu) {
           E.valu("v_mov_b32_e32 " + VL(r[j]) + ", " + imm(v));
           continue;
         }
-        E.valu("v_and_b32_e32 " + VL(r[j]) + ", " + imm(~m) + ", " + VL(r[j]));
+        if (m) E.valu("v_and_b32_e32 " + VL(r[j]) + ", " + imm(~m) + ", " + VL(r[j]));
         if (v) E.valu("v_or_b32_e32 " + VL(r[j]) + ", " + imm(v) + ", " + VL(r[j]));
         continue;
       }
@@ -2971,9 +2971,12 @@ struct Gen {
         r[j] = Lit(x);
         continue;
       }
-      const Limb a = and_lit(r[j], ~m);
-      drop(r[j]);
-      r[j] = a;
+      Limb a = r[j];
+      if (m) {
+        a = and_lit(r[j], ~m);
+        drop(r[j]);
+        r[j] = a;
+      }
       if (v) {
         const Limb d = fresh();
         E.valu("v_or_b32_e32 " + VL(d) + ", " + imm(v) + ", " + VL(a));
@@ -3132,13 +3135,13 @@ struct Gen {
           const uint32_t f = fix - 1;
           for (uint32_t j = 0; j < Lc; j++) {
             const uint32_t m = G[f + j], v = G[f + Lc + j];
-            if (!m) continue;
+            if (!m && !v) continue;  // (the value's bits count outside the mask too)
             if (!r[j].reg() || m == 0xFFFFFFFFu) {
               drop(r[j]);
               r[j] = Lit(v);
               continue;
             }
-            E.valu("v_and_b32_e32 " + VL(r[j]) + ", " + imm(~m) + ", " + VL(r[j]));
+            if (m) E.valu("v_and_b32_e32 " + VL(r[j]) + ", " + imm(~m) + ", " + VL(r[j]));
             if (v) E.valu("v_or_b32_e32 " + VL(r[j]) + ", " + imm(v) + ", " + VL(r[j]));
           }
         }

@@ -1530,10 +1530,16 @@ struct Analysis {
     const auto& G = *gconsts;
     const U256 wlim = U256::ones(w);
     auto lim = [&](uint32_t off, U256* x) { return U256::from_limbs(&G[off], L, x); };
+    // a FIXED value or a dictionary entry: the generator masks what it reads to the width
+    auto ent = [&](uint32_t off, U256* x) {
+      if (!lim(off, x)) return false;
+      *x = *x & wlim;
+      return true;
+    };
     switch (kind) {
       case MG_GEN_FIXED: {
         U256 x;
-        if (lim(sp.p[0], &x)) v = vexact(x, w);
+        if (ent(sp.p[0], &x)) v = vexact(x, w);
         break;
       }
       case MG_GEN_DICT:
@@ -1542,7 +1548,7 @@ struct Analysis {
         bool ok = sp.p[1] > 0;
         for (uint32_t e = 0; ok && e < sp.p[1]; e++) {
           U256 x;
-          if (!lim(sp.p[0] + e * L, &x)) ok = false;
+          if (!ent(sp.p[0] + e * L, &x)) ok = false;
           else d.push_back(x);
         }
         Rng dh;
@@ -1663,14 +1669,15 @@ struct Analysis {
         break;
     }
     tighten(v, w);
-    if (const uint32_t fix = sp.kind >> 8) {  // (v & ~m) | val
+    if (const uint32_t fix = sp.kind >> 8) {  // (v & ~m) | val, val within the width but not within m
       U256 m, fv;
       if (U256::from_limbs(&G[fix - 1], L, &m) && U256::from_limbs(&G[fix - 1 + L], L, &fv)) {
         m = m & wlim;
-        fv = fv & m;
+        fv = fv & wlim;
         Val f;
         f.kb.k = true;
-        f.kb.z = (v.kb.z & ~m) | (m & ~fv);
+        // one where val is; zero where val is not and the mask clears the bit or v has it zero
+        f.kb.z = (v.kb.z | m) & ~fv;
         f.kb.o = (v.kb.o & ~m) | fv;
         if (v.has_set) {
           f.has_set = true;
@@ -2247,6 +2254,11 @@ int parse_gen(const Lowered& prog, const uint32_t* blob, size_t n_words, std::ve
     const uint32_t fix = s.kind >> 8;
     if (fix && !in_range(fix - 1, 2ull * L)) {
       err = "fixed-bit record out of range";
+      return MG_E_INVALID;
+    }
+    // the record is applied after the mask to the width, so its value must fit the width itself
+    if (fix && (prog.coord_width[c] & 31u) && (consts[fix - 1 + 2 * L - 1] >> (prog.coord_width[c] & 31u)) != 0) {
+      err = "fixed-bit value exceeds the coordinate width";
       return MG_E_INVALID;
     }
     switch (s.kind & 0xFFu) {

@@ -161,4 +161,16 @@ def coords_from_soa(soa: np.ndarray, widths: Sequence[int], i: int) -> List[int]
 
 
 def verdicts(spec: Dict, soa: np.ndarray, coord_widths: Sequence[int], n: int) -> np.ndarray:
-    return np.array([run(spec, coords_from_soa(soa, coord_widths, i)) for i in range(n)], dtype=np.uint8)
+    # plain lists once, not a numpy scalar per instruction word and candidate
+    spec = dict(spec, code=np.asarray(spec["code"]).tolist(), consts=np.asarray(spec["consts"]).tolist(),
+                aux=np.asarray(spec["aux"]).tolist())
+    cols = np.asarray(soa)[:, :n].T.tolist()
+    out = []
+    for col in cols:
+        coords, row = [], 0
+        for w in coord_widths:
+            L = (w + 31) // 32
+            coords.append(_limbs_to_int(col[row:row + L]))
+            row += L
+        out.append(run(spec, coords))
+    return np.array(out, dtype=np.uint8)
