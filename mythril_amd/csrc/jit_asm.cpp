@@ -420,6 +420,201 @@ struct Gen {
     for (size_t k = 0; k < v.size(); k++)
       if (!done[k]) visit((int32_t)k);
     code.swap(out);
+    guards.clear();
+    if (lazy && !eval_kernel) plan_lazy();
+  }
+
+  // ---------------------------------------------------------------------------------------
+  // lazy select arms
+  // ---------------------------------------------------------------------------------------
+  // A wide ITE whose condition is false in every lane of the group yields its else operand in every
+  // lane: the true arm's value is then never read, and neither is anything computed for it alone.
+  // The arm's exclusive cone is the set of instructions (K_COORD generation included) whose every
+  // reader lies in the cone or is the ITE reading it as that arm; a guarded ITE is emitted as
+  //     condition mask ; unguarded operand ; s_cmp_eq_u64 mask, 0 ; s_cbranch_scc1 skip ;
+  //     the cone ; v_cndmask per limb into the unguarded operand's registers ; skip:
+  // so a group no lane of which takes the arm pays one scalar compare and a branch for it (an
+  // aliasing store chain's reads: C2's balances[sender2] through tx 1's stores is all-false in 0.81-
+  // 0.85 of the groups, tools/lazy_share.py).  The else arm is guarded the same way on "every lane
+  // true" (s_cmp_eq_u64 mask, -1).  plan_lazy moves each guarded cone to just before its ITE (its
+  // members have no other reader, so every definition still precedes its uses) and records the
+  // region; body() opens it, the ITE closes it.  Rules:
+  //  * a coordinate that is some coordinate's COPY source, or that the program generates twice, stays
+  //    outside every cone (the generator reads it by name, not through an operand edge); so do the
+  //    data-dependent loops (division, EXP, Keccak), which keep their own regions;
+  //  * an arm two instructions read has an empty cone, and an ITE without a cone stays as it is;
+  //  * one guard per ITE: the true arm's when it qualifies (an aliasing chain's conditions are rarely
+  //    true), else the else arm's;
+  //  * the result is selected in place into the unguarded operand's registers where they die at the
+  //    ITE; otherwise it takes fresh registers, copied before the branch.  A guard qualifies when the
+  //    cone's static VALU estimate (op_weight) plus the selects is at least lazy_min() plus those
+  //    copies; an else arm only without copies (no condition was all-true in any measured group, so
+  //    its guard may cost a scalar compare, never VALU);
+  //  * a region is a conditional region like the generator's: no cache entry is made inside, no mask
+  //    moves to its VGPR form, SGPR pairs are reserved before the outermost branch, the join is a
+  //    label (every VALU-written SGPR fresh, pending LDS reads waited for).  A Bool defined before
+  //    the region that gained its other form (mask <-> limb) inside loses it again at the join.
+  // Search and generated-verdict kernels only; the eval and read-back kernels (eval_kernel) keep the
+  // program's order for their row queue.  MYTHGPU_JIT_ASM_NO_LAZY=1: off (the emitted text is then
+  // what it was before this pass existed); MYTHGPU_JIT_ASM_LAZY_MIN=N: the threshold (default 8).
+  bool lazy = true;  // jit_asm_source: off by the switch, and for the retry of a kernel that failed with it
+  static bool no_lazy() {
+    static const bool on = [] {
+      const char* g = getenv("MYTHGPU_JIT_ASM_NO_LAZY");
+      return g && g[0] == '1';
+    }();
+    return on;
+  }
+  static uint32_t lazy_min() {
+    static const uint32_t n = [] {
+      const char* g = getenv("MYTHGPU_JIT_ASM_LAZY_MIN");
+      return g ? (uint32_t)std::max(0, atoi(g)) : 8u;
+    }();
+    return n;
+  }
+  static uint32_t lazy_priors() {
+    static const uint32_t n = [] {
+      const char* g = getenv("MYTHGPU_JIT_ASM_LAZY_PRIORS");
+      return g ? (uint32_t)std::max(0, std::min(8, atoi(g))) : 1u;
+    }();
+    return n;
+  }
+  struct Guard {
+    uint32_t dst = MG_NONE;  // the ITE's result
+    uint32_t size = 0;       // instructions of the cone, contiguous before the ITE
+    bool true_arm = true;
+    uint32_t weight = 0;     // the cone's static VALU estimate
+    int32_t ite = -1, begin = -1;  // code indices (final order)
+  };
+  std::vector<Guard> guards;
+  std::vector<int32_t> guard_of;                  // code index of an ITE -> its guard, or -1
+  std::vector<std::vector<int32_t>> guard_begin;  // code index -> the guards opening there, outermost first
+  template <class F>
+  void reads(const Instr& in, F&& f) const {
+    auto r = [&](uint32_t id) {
+      if (id != MG_NONE && id < P.vwidth.size()) f(id);
+    };
+    switch (in.op) {
+      case K_CONST: case K_COORD: break;
+      case K_LOOKUP:
+        r(in.a);
+        r(in.p0);
+        for (uint32_t q = 0; q < 2 * in.c; q++) r(P.vaux[in.p1 + q]);
+        break;
+      case K_NOT: case K_NEG: case K_EXTRACT: case K_ZEXT: case K_SEXT: case K_ASSERT: case K_COPY: case K_WATCH:
+        r(in.a);
+        break;
+      case K_ITE:
+        r(in.a);
+        r(in.b);
+        r(in.c);
+        break;
+      default:
+        r(in.a);
+        r(in.b);
+        break;
+    }
+  }
+  void plan_lazy() {
+    const size_t nv = P.vwidth.size(), n = code.size();
+    std::vector<char> fixed_coord(specs.size(), 0);  // COPY sources and coordinates generated twice
+    {
+      std::vector<uint32_t> times(specs.size(), 0);
+      for (const GenSpec& sp : specs)
+        if ((sp.kind & 0xFFu) == MG_GEN_MIXED && sp.p[3] != MG_NONE && sp.p[3] < specs.size()) fixed_coord[sp.p[3]] = 1;
+      for (const Instr& in : code)
+        if (in.op == K_COORD && in.p0 < specs.size() && ++times[in.p0] > 1) fixed_coord[in.p0] = 1;
+    }
+    std::vector<uint32_t> defs(nv, 0);
+    for (const Instr& in : code)
+      if (in.dst != MG_NONE && in.dst < nv) defs[in.dst]++;
+    std::vector<std::vector<int32_t>> users(nv);
+    auto index_users = [&]() {
+      for (auto& u : users) u.clear();
+      for (size_t p = 0; p < n; p++) reads(code[p], [&](uint32_t id) { users[id].push_back((int32_t)p); });
+    };
+    index_users();
+    std::vector<char> in_cone(n, 0);
+    // the exclusive cone of `arm` below the ITE at K (marks in_cone, returns its members in order)
+    auto cone_of = [&](int32_t K, uint32_t arm, std::vector<int32_t>& cone, uint32_t& weight) {
+      cone.clear();
+      weight = 0;
+      for (int32_t p = K - 1; p >= 0; p--) {
+        in_cone[p] = 0;
+        const Instr& in = code[p];
+        const uint32_t d = in.dst;
+        if (d == MG_NONE || d >= nv || defs[d] != 1 || users[d].empty() || heavy_op(in.op)) continue;
+        if (in.op == K_COORD && (in.p0 >= specs.size() || fixed_coord[in.p0])) continue;
+        bool all = true;
+        for (int32_t u : users[d]) all = all && (u == K ? d == arm : (u < K && in_cone[u]));
+        if (!all) continue;
+        in_cone[p] = 1;
+        cone.push_back(p);
+        if (in.op != K_CONST) weight += op_weight(in);
+      }
+      std::reverse(cone.begin(), cone.end());
+    };
+    std::vector<int32_t> cone, cone2;
+    std::vector<Instr> moved;
+    for (int32_t K = 0; K < (int32_t)n; K++) {
+      const Instr in = code[K];
+      if (in.op != K_ITE || in.dst == MG_NONE || in.dst >= nv || P.vwidth[in.dst] <= 1 || defs[in.dst] != 1) continue;
+      if (in.a == in.b || in.a == in.c || in.b == in.c || in.a >= nv || in.b >= nv || in.c >= nv) continue;
+      const uint32_t Ld = L(in.dst);
+      bool taken = false;
+      for (int t = 0; t < 2 && !taken; t++) {
+        const bool true_arm = t == 0;
+        const uint32_t arm = true_arm ? in.b : in.c, other = true_arm ? in.c : in.b;
+        uint32_t weight = 0;
+        cone_of(K, arm, cone, weight);
+        if (cone.empty()) continue;
+        bool dies = true;  // the unguarded operand's last reader is this ITE (or in the cone before it)
+        for (int32_t u : users[other]) dies = dies && u <= K;
+        const uint32_t copies = dies ? 0u : Ld;
+        if (!true_arm && copies) continue;
+        if (weight + Ld < lazy_min() + copies) continue;
+        // the cone, in order, to just before the ITE
+        const int32_t lo = cone.front();
+        moved.clear();
+        for (int32_t p = lo; p < K; p++)
+          if (!in_cone[p]) moved.push_back(code[p]);
+        for (int32_t p : cone) moved.push_back(code[p]);
+        std::copy(moved.begin(), moved.end(), code.begin() + lo);
+        Guard g;
+        g.dst = in.dst;
+        g.size = (uint32_t)cone.size();
+        g.true_arm = true_arm;
+        g.weight = weight;
+        guards.push_back(g);
+        index_users();
+        taken = true;
+      }
+    }
+    // final positions; a guard whose condition or unguarded operand is not defined before its region
+    // (never by construction) is dropped
+    std::vector<int32_t> at(nv, -1);
+    for (size_t p = 0; p < n; p++)
+      if (code[p].dst != MG_NONE && code[p].dst < nv && at[code[p].dst] < 0) at[code[p].dst] = (int32_t)p;
+    guard_of.assign(n, -1);
+    guard_begin.assign(n, {});
+    std::vector<Guard> kept;
+    for (Guard g : guards) {
+      g.ite = at[g.dst];
+      g.begin = g.ite - (int32_t)g.size;
+      const Instr& in = code[g.ite];
+      const uint32_t other = g.true_arm ? in.c : in.b;
+      if (g.begin < 0 || at[in.a] >= g.begin || at[other] >= g.begin) continue;
+      kept.push_back(g);
+    }
+    guards.swap(kept);
+    // outermost first where two regions open at one instruction: the later ITE encloses the earlier
+    std::vector<int32_t> order(guards.size());
+    for (size_t i = 0; i < order.size(); i++) order[i] = (int32_t)i;
+    std::sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return guards[x].ite > guards[y].ite; });
+    for (int32_t i : order) {
+      guard_of[guards[i].ite] = i;
+      guard_begin[guards[i].begin].push_back(i);
+    }
   }
   // Search kernels: constraints whose not-yet-emitted cone holds a heavy operator (Keccak, EXP,
   // division: hundreds to thousands of VALU per candidate) go after the light ones.  The early exit after each ASSERT
@@ -1837,6 +2032,7 @@ struct Gen {
   // the body's counts, a comment after the kernel's last instruction (tests read them)
   void mcache_note() {
     E.o << "  ; mask cache: " << mc_hits << " hits, " << mc_evictions << " evictions, " << mc_spills << " mask spills\n";
+    if (lazy && !eval_kernel) E.o << "  ; lazy arms: " << lazy_regions << " guarded regions\n";
   }
   // SGPR pairs only the cache holds: free for the asking (salloc evicts them)
   int mcache_spare() const {
@@ -1875,7 +2071,7 @@ struct Gen {
     for (uint32_t j = 0; j < Lk; j++) prs.push_back({limb(a, j), limb(b, j)});
     Limb keep{};
     const Mask m = eq_mask(prs, &keep);
-    if (keep.reg() && caches) {
+    if (keep.reg() && caches && !cond) {  // (a difference computed under a branch is not defined after the join)
       eqdiff[key] = keep;
       eq_last[key] = ++tick;
     }
@@ -3382,6 +3578,117 @@ struct Gen {
   }
   uint32_t demanded(uint32_t d) const { return need[d] ? 64 - (uint32_t)__builtin_clzll(need[d]) : 0; }
 
+  // ---- guarded selects (plan_lazy) -----------------------------------------------------------
+  // An open region: the result's registers hold the unguarded operand's limbs on both paths, the
+  // select at the region's end overwrites them in the lanes that take the arm.
+  struct Region {
+    bool active = false;
+    Mask c;                 // the condition (a reference of the region's own)
+    bool true_arm = true;   // the arm selected where the mask is set
+    std::vector<Limb> r;    // the result's limbs
+    std::string skip;
+    std::vector<std::pair<uint32_t, uint8_t>> bools;  // live Bools at the branch: bit 0 mask form, bit 1 limb form
+  };
+  std::vector<Region> regions;  // by guard
+  uint32_t lazy_regions = 0;    // regions emitted (the kernel's trailing comment)
+  // Opens a region skipped when mask `c` (an SGPR pair) is 0 in every lane (true_arm) or set in every
+  // lane: result `d` starts as the unguarded value `u`, in place where u's register dies at `k`.
+  bool in_place(const Limb& x, uint32_t u, size_t k) const {
+    return x.reg() && (int)x.v >= E.vfirst && E.vref[x.v] == 1 && last[u] <= (int32_t)k;
+  }
+  // limbs of result d that cannot start in u's registers (literals, registers something else holds
+  // or u lives on in): each is a v_mov on both paths
+  uint32_t region_copies(uint32_t u, uint32_t d, size_t k) {
+    uint32_t n = 0;
+    for (uint32_t j = 0; j < L(d); j++)
+      if (need[d] >> j & 1) n += !in_place(limb(u, j), u, k);
+    return n;
+  }
+  void region_open(Region& rg, const Mask& c, bool true_arm, uint32_t u, uint32_t d, size_t k) {
+    rg = Region{};
+    rg.active = true;
+    rg.c = c;
+    rg.true_arm = true_arm;
+    E.sretain(c);
+    const uint32_t Ld = L(d);
+    rg.r.assign(Ld, Limb{});
+    for (uint32_t j = 0; j < Ld; j++) {
+      if (!(need[d] >> j & 1)) continue;
+      const Limb x = limb(u, j);
+      if (in_place(x, u, k)) {
+        E.retain(x);
+        rg.r[j] = x;
+      } else {
+        const Limb f = fresh();
+        E.valu("v_mov_b32_e32 " + VL(f) + ", " + src(x));
+        rg.r[j] = f;
+      }
+    }
+    for (uint32_t id = 0; id < val.size(); id++) {
+      const Val& x = val[id];
+      if (!x.def || P.vwidth[id] != 1) continue;
+      rg.bools.push_back({id, (uint8_t)((x.m.k ? 1 : 0) | ((!x.l.empty() && x.l[0].k != LU) ? 2 : 0))});
+    }
+    rg.skip = E.newlab();
+    cond++;
+    lazy_regions++;
+    note(true_arm ? "lazy:guard" : "lazy:guard-else");
+    E.salu("s_cmp_eq_u64 " + SP(c.s) + ", " + (true_arm ? "0" : "-1"));
+    E.ctl("s_cbranch_scc1 " + rg.skip);
+    note("lazy:region");
+  }
+  // The selects of arm value `arm` into the result, the join, and the result as value d
+  void region_select(Region& rg, uint32_t arm, const Mask* by = nullptr) {
+    {  // the tag carries the selects' number: their simulated count over it is the share of groups that
+       // took the region (tools/asm_count.py)
+      size_t n = 0;
+      for (const Limb& l : rg.r) n += l.k != LU;
+      note(("lazy:select x" + std::to_string(n)).c_str());
+    }
+    const Mask& m = by ? *by : rg.c;
+    for (uint32_t j = 0; j < rg.r.size(); j++) {
+      if (rg.r[j].k == LU) continue;
+      const Limb a = v3(limb(arm, j));
+      const std::string f = rg.true_arm ? VL(rg.r[j]) : src(a), t = rg.true_arm ? src(a) : VL(rg.r[j]);
+      E.valu("v_cndmask_b32_e64 " + VL(rg.r[j]) + ", " + f + ", " + t + ", " + SP(m.s), {m.s, m.s + 1});
+      drop(a);
+    }
+  }
+  void region_close(Region& rg, uint32_t d) {
+    E.label(rg.skip);
+    cond--;
+    // a Bool from before the branch keeps only the forms it had there: one made inside was written
+    // on the taken path alone
+    for (const auto& b : rg.bools) {
+      Val& x = val[b.first];
+      if (!x.def) continue;
+      if (!(b.second & 1) && x.m.k) {
+        E.srelease(x.m);
+        x.m = Mask{};
+      }
+      if (!(b.second & 2) && !x.l.empty()) {
+        for (auto& l : x.l) drop(l);
+        x.l.clear();
+      }
+    }
+    E.srelease(rg.c);
+    rg.active = false;
+    set(d, rg.r);
+  }
+  void guard_open(int32_t gi) {
+    const Guard& gd = guards[gi];
+    const Instr& in = code[gd.ite];
+    Region& rg = regions[gi];
+    rg = Region{};
+    if (!cond) sreserve();
+    const Mask c = mask_of(in.a);
+    if (c.k != 2) return;  // the same in every lane at emission time: a plain ITE picks the operand
+    // the copies as they stand now (plan_lazy saw the order before later cones moved, and no literals)
+    const uint32_t u = gd.true_arm ? in.c : in.b, copies = region_copies(u, in.dst, (size_t)gd.ite);
+    if ((!gd.true_arm && copies) || gd.weight + L(in.dst) < lazy_min() + copies) return;
+    region_open(rg, c, gd.true_arm, gd.true_arm ? in.c : in.b, in.dst, (size_t)gd.ite);
+  }
+
   // ---------------------------------------------------------------------------------------
   // data-dependent operators: variable shifts, division by a non-literal, EXP, Keccak-256.
   // Values are <= 256 bits here (the lowering's bound), so they live in <= 8 limbs; loops are
@@ -4735,6 +5042,12 @@ struct Gen {
           E.srelease(f);
           break;
         }
+        if (!guards.empty() && guard_of[k] >= 0 && regions[guard_of[k]].active) {  // the region's end
+          Region& rg = regions[guard_of[k]];
+          region_select(rg, rg.true_arm ? in.b : in.c);
+          region_close(rg, d);
+          break;
+        }
         std::vector<Limb> r(Ld);
         if (c.k == 1) {
           for (uint32_t j = 0; j < Ld; j++) {
@@ -4911,6 +5224,40 @@ struct Gen {
           }
           set_mask(d, cur);
           break;
+        }
+        // No prior's key matches in any lane of the group: the default in every lane.  Guarded like an
+        // ITE's true arm (plan_lazy) on the OR of the key tests when the default's registers die here,
+        // so the skipped path costs the scalar compare and a branch for the select chain it drops.
+        // One prior by default (C2's single-prior 256-bit lookup matches in no lane of 0.80-0.855 of the
+        // groups, its two-prior one in some lane of every group): MYTHGPU_JIT_ASM_LAZY_PRIORS=N guards
+        // lookups of up to N priors
+        if (lazy && !eval_kernel && n >= 1 && n <= lazy_priors() && last[in.p0] <= (int32_t)k &&
+            (uint32_t)__builtin_popcountll(need[d] & lowmask(Ld)) * n >=
+                std::max(1u, lazy_min()) + region_copies(in.p0, d, k)) {
+          if (!cond) sreserve();
+          std::vector<Mask> hs(n);
+          bool pairs = true;
+          for (uint32_t p = 0; p < n; p++) {
+            hs[p] = key_test(P.vaux[in.p1 + 2 * p]);
+            pairs = pairs && hs[p].k == 2;
+          }
+          if (pairs) {
+            Mask any = hs[0];
+            E.sretain(any);
+            for (uint32_t p = 1; p < n; p++) {
+              const Mask o = mop("or", any, hs[p]);
+              E.srelease(any);
+              any = o;
+            }
+            Region rg;
+            region_open(rg, any, true, in.p0, d, k);
+            E.srelease(any);  // (the region holds its own reference)
+            for (int32_t p = (int32_t)n - 1; p >= 0; p--) region_select(rg, P.vaux[in.p1 + 2 * p + 1], &hs[p]);
+            for (auto& h : hs) E.srelease(h);
+            region_close(rg, d);
+            break;
+          }
+          for (auto& h : hs) E.srelease(h);  // a test decided at emission time: the plain chain
         }
         // (the key tests and their run ORs stay in SGPR pairs over the limbs: only with room for them)
         if (n >= 2 && n <= 5 && !no_lookup_runs() && E.sfree() + mcache_spare() >= (int)(n + n * (n - 1) / 2 + 4)) {
@@ -5186,10 +5533,15 @@ struct Gen {
     // short of SGPR pairs: the mask cache's entries go first, then a live Bool moves to its VGPR form
     E.on_spressure = [this]() { return mcache_evict() || spill_mask(); };
     lvn_on = true;
+    cond = 0;  // (a kernel abandoned inside a guarded region left it open)
+    regions.assign(guards.size(), Region{});
+    lazy_regions = 0;
     static const bool annotate = getenv("MYTHGPU_JIT_ASM_ANNOTATE") != nullptr;
     for (size_t k = 0; k < code.size(); k++) {
       const Instr& in = code[k];
       cur_k = k;
+      if (!guards.empty())
+        for (int32_t gi : guard_begin[k]) guard_open(gi);
       if (is_view(in.dst)) continue;  // read through by its one reader (field_of)
       if (annotate)
         E.o << "  ; vcode " << k << " op " << in.op << " w " << in.wd << " dst " << in.dst << " a " << in.a << " b " << in.b
@@ -6182,6 +6534,8 @@ static int occupancy_step(int v) {
   return std::max(floor_v, std::min(256, 512 / waves / 8 * 8));
 }
 
+static std::string search_kernels(Gen& g, uint32_t kernels, bool strict);
+
 int jit_asm_source(const Lowered& P, const std::vector<GenSpec>& specs, const std::vector<uint32_t>& gconsts,
                    uint32_t kernels, std::string& out, std::string& err) {
   try {
@@ -6315,6 +6669,37 @@ int jit_asm_source(const Lowered& P, const std::vector<GenSpec>& specs, const st
       out = o.str();
       return MG_OK;
     }
+    // Guarded select arms (Gen::plan_lazy): a kernel that fails with them (a region short of SGPR
+    // pairs) is emitted once more without, as it was before they existed
+    g.lazy = !Gen::no_lazy();
+    if (g.lazy) {
+      std::string o2;
+      try {
+        o2 = search_kernels(g, kernels, true);
+      } catch (const AsmFail&) {
+        o2.clear();
+      }
+      if (!o2.empty()) {
+        out = o.str() + o2;
+        return MG_OK;
+      }
+    }
+    Gen g0(P, specs, gconsts);
+    g0.lazy = false;
+    out = o.str() + search_kernels(g0, kernels, false);
+    return MG_OK;
+  } catch (const AsmFail& f) {
+    err = f.why;
+    return MG_E_UNSUPPORTED;
+  } catch (const std::exception& x) {
+    err = std::string("assembly tier: ") + x.what();
+    return MG_E_UNSUPPORTED;
+  }
+}
+
+static std::string search_kernels(Gen& g, uint32_t kernels, bool strict) {
+  std::ostringstream o;
+  {
     g.analyse();
     // pass 1, without the value caches, counts the literals the kernel moves into VGPRs and its VGPRs;
     // pass 2 pools the most used literals and runs the caches within the occupancy step pass 1 reached
@@ -6328,12 +6713,16 @@ int jit_asm_source(const Lowered& P, const std::vector<GenSpec>& specs, const st
       v0 = g.meta_vgpr["mgj_search"];
       if (getenv("MYTHGPU_JIT_ASM_VREPORT")) fprintf(stderr, "mythgpu asm: pass-1 VGPRs %d\n", v0);
     } catch (const AsmFail&) {
+      if (strict) throw;
       // out of VGPRs without the caches (shared XOR limbs relieve pressure): no soft limit then
       v0 = 256;
       g.census.clear();
     }
     g.caches = true;
     g.vsoft = occupancy_step(v0);
+    // a guarded kernel that fits eight waves without the caches keeps them with the caches: a region
+    // holds its result's registers across the cone, which the caches would otherwise fill past 64
+    if (g.lazy && !g.guards.empty() && v0 <= 64) g.vsoft = 64;
     // the group key's unit (Gen::sgkey): the scalar unit unless the first pass's body leans on it
     if (Gen::sgkey_env() >= 0) {
       g.sgkey = Gen::sgkey_env() == 1;
@@ -6371,15 +6760,8 @@ int jit_asm_source(const Lowered& P, const std::vector<GenSpec>& specs, const st
       o << g.kernel("mgj_gen");
     }
     o << metadata(g.meta_vgpr, g.meta_sgpr, with_gen, g.meta_lds);
-    out = o.str();
-    return MG_OK;
-  } catch (const AsmFail& f) {
-    err = f.why;
-    return MG_E_UNSUPPORTED;
-  } catch (const std::exception& x) {
-    err = std::string("assembly tier: ") + x.what();
-    return MG_E_UNSUPPORTED;
   }
+  return o.str();
 }
 
 }  // namespace mg

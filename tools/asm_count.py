@@ -2,9 +2,10 @@
 every workload, a full-evaluation launch (no early exit) over a window of 64-candidate groups, VALU
 and SALU lane-instructions per candidate (the PMC's SQ_INSTS_VALU x 64 / candidates, without a GPU).
 
-  python tools/asm_count.py [workload ...] [--env K=V ...]"""
+  python tools/asm_count.py [workload ...] [--env K=V ...]   (ASMSIM_SEED / ASMSIM_START / ASMSIM_GROUPS: the window)"""
 import os
 import random
+import re
 import subprocess
 import sys
 from pathlib import Path
@@ -32,7 +33,9 @@ def main():
     exe = _cached(TPF(), sanitize=False)
     for name in names:
         P, blob = search.prepare([c.raw for c in workloads.WORKLOADS[name]()])
-        rec = record(0, P.to_bytes(), blob, 7, 1 << 40, 64 * 64)
+        # ASMSIM_SEED / ASMSIM_START / ASMSIM_GROUPS: the window (default seed 7, 64 groups from 2^40)
+        rec = record(0, P.to_bytes(), blob, int(env.get("ASMSIM_SEED", "7"), 0), int(env.get("ASMSIM_START", str(1 << 40)), 0),
+                     64 * int(env.get("ASMSIM_GROUPS", "64"), 0))
         r = subprocess.run([str(exe)], input=rec, capture_output=True, env=env)
         line = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("count record")]
         summ = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("records=")]
@@ -46,6 +49,12 @@ def main():
                 t, v = ln[len("count tag "):].rsplit(":", 1)
                 va, _, sa = v.strip().partition(" salu ")
                 tags.append((float(va), float(sa or 0), t.strip()))
+        # guarded select arms (jit_asm.cpp: plan_lazy): a region's select tag names its selects, so their
+        # simulated count over that number is the share of all groups that took the region
+        for v, sv, t in tags:
+            m = re.match(r"vcode (\d+) lazy:select x(\d+)$", t)
+            if m and int(m.group(2)):
+                print(f"  guard closing at vcode {m.group(1)}: region taken by {v / int(m.group(2)):.3f} of the groups")
         key = (lambda x: x[1]) if env.get("ASMSIM_SORT") == "salu" else (lambda x: x[0])
         for v, sv, t in sorted(tags, key=key, reverse=True)[:int(env.get("ASMSIM_TOP", "40"))]:
             print(f"  {v:8.2f} {sv:8.2f}  {t}")
