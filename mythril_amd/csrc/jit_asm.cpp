@@ -2767,7 +2767,9 @@ struct Gen {
     const uint32_t Lc = Lw(w), Lu = std::min(Lc, upto);
     std::vector<Limb> r(Lc, Lit(0));
     auto dst = [&](uint32_t j) { return tgt ? (*tgt)[j] : fresh(); };
-    if (w <= 32 && n && (uint64_t)n * w <= 32) {  // packed in one literal: one bit-field extract
+    // packed in one literal: one bit-field extract.  Not at w == 32 (one entry): v_bfe_u32 reads its
+    // field width from src2[4:0], so 32 would extract nothing; that entry is the literal of the branch below
+    if (w < 32 && n && (uint64_t)n * w <= 32) {
       uint32_t pack = 0;
       const uint32_t m = w == 32 ? 0xFFFFFFFFu : ((1u << w) - 1u);
       for (uint32_t e2 = 0; e2 < n; e2++) pack |= (G[off + e2] & m) << (e2 * w);
@@ -6670,13 +6672,16 @@ int jit_asm_source(const Lowered& P, const std::vector<GenSpec>& specs, const st
       return MG_OK;
     }
     // Guarded select arms (Gen::plan_lazy): a kernel that fails with them (a region short of SGPR
-    // pairs) is emitted once more without, as it was before they existed
+    // pairs) is emitted once more without, as it was before they existed.  Under MYTHGPU_JIT_ASM_CHECK
+    // the emitter's own "internal:" failures (the lifetime checker's among them) are not retried: a
+    // lifetime bug inside a region must show, not turn into a kernel without regions
     g.lazy = !Gen::no_lazy();
     if (g.lazy) {
       std::string o2;
       try {
         o2 = search_kernels(g, kernels, true);
-      } catch (const AsmFail&) {
+      } catch (const AsmFail& f) {
+        if (Emitter::check_on() && f.why.rfind("internal:", 0) == 0) throw;
         o2.clear();
       }
       if (!o2.empty()) {

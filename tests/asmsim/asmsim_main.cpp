@@ -113,6 +113,10 @@ std::string check_search(uint64_t rec, const std::vector<uint8_t>& prog, const s
     Tm tm(0);
     rc = jit_asm_source(sp, specs, consts, JIT_SEARCH | JIT_GEN, src, err);
   }
+  if (rc == MG_E_UNSUPPORTED && err.rfind("internal:", 0) == 0) {  // the emitter's own checks: a bug, not a refusal
+    C.asmerror++;
+    return "emitter: " + err;
+  }
   if (rc == MG_E_UNSUPPORTED) {
     C.outside++;
     if (getenv("ASMSIM_WHY")) fprintf(stderr, "outside the tier: %s\n", err.c_str());
@@ -282,6 +286,10 @@ std::string check_eval(const std::vector<uint8_t>& prog, uint64_t seed, uint32_t
       fclose(fp);
       rc = MG_OK;
     }
+  }
+  if (rc == MG_E_UNSUPPORTED && err.rfind("internal:", 0) == 0) {  // the emitter's own checks: a bug, not a refusal
+    C.asmerror++;
+    return "emitter: " + err;
   }
   if (rc == MG_E_UNSUPPORTED) {
     C.outside++;
