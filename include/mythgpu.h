@@ -484,8 +484,10 @@ int mg_jit_helper_pid(void);
  * gen = 0, the eval kernel (mg_jit_eval*).  It emits straight-line code (values in VGPRs, literals as immediates,
  * generator inlined).  Same semantics as mg_search / mg_eval. */
 /* host-only: the specialised source (search kernel if gen_blob, else eval kernel); compile bit 0:
- * also compile it, bit 1: the eval kernel for the tiled SoA (MG_JIT_SOA_TILED).  Same bits for
- * mg_program_jit_asm. */
+ * also compile it, bit 1: the eval kernel for the tiled SoA (MG_JIT_SOA_TILED), bit 2 (4, with a
+ * gen_blob): also build mgj_gen, the per-candidate verdict kernel, as MG_JIT_GEN_VERDICTS does for
+ * mg_jit_compile_ex (ignored for the eval kernel).  Bits 0 and 1 mean the same for
+ * mg_program_jit_asm, whose search text always holds mgj_gen. */
 int mg_program_jit_source(const uint8_t* ssa, size_t len, const uint32_t* gen_blob, size_t gen_words, int compile,
                           char* buf, size_t cap, size_t* out_len);
 /* host-only: the first tier's assembly (search + gen kernels with a generator blob, else the eval

@@ -3696,7 +3696,7 @@ int mg_program_jit_source(const uint8_t* ssa, size_t len, const uint32_t* gen_bl
   rc = specialize_program(low, gen_blob ? &specs : nullptr, gen_blob ? &consts : nullptr, sp, err,
                           /*keep_watch=*/gen_blob == nullptr);
   if (rc) return set_err(rc, err);
-  const std::string src = gen_blob ? jit_source(sp, &specs, &consts, JIT_SEARCH)
+  const std::string src = gen_blob ? jit_source(sp, &specs, &consts, JIT_SEARCH | ((compile & 4) ? JIT_GEN : 0u))
                                    : jit_source(sp, nullptr, nullptr, JIT_EVAL | ((compile & 2) ? JIT_EVAL_TILED : 0u));
   if (out_len) *out_len = src.size();
   if (buf && cap) {

@@ -388,17 +388,21 @@ def specialized_program(blob: bytes, gen_blob: Optional[np.ndarray] = None, keep
     return {"code": code, "consts": consts, "aux": aux, "widths": widths, "n_coords": ncoord}
 
 
-def jit_source(blob: bytes, gen_blob: Optional[np.ndarray] = None, compile: bool = False, tiled: bool = False) -> str:
+def jit_source(blob: bytes, gen_blob: Optional[np.ndarray] = None, compile: bool = False, tiled: bool = False,
+               gen_verdicts: bool = False) -> str:
     """Host-only: the specialised HIP source of a program — the search kernel when a
-    generator blob is given, else the eval kernel — optionally hipRTC-compiled (no GPU)."""
+    generator blob is given, else the eval kernel — optionally hipRTC-compiled (no GPU).
+    ``gen_verdicts`` (search only): the source also holds ``mgj_gen``, the per-candidate verdict
+    kernel ``jit_compile(..., gen_verdicts=True)`` builds."""
     lib = load_library()
     g = None if gen_blob is None else np.ascontiguousarray(gen_blob, dtype=np.uint32)
     gp = _ptr(g, C.c_uint32) if g is not None else None
     gn = 0 if g is None else g.size
     n = C.c_size_t()
-    _check(lib.mg_program_jit_source(_u8(blob), len(blob), gp, gn, 2 if tiled else 0, None, 0, C.byref(n)))
+    bits = (2 if tiled else 0) | (4 if gen_verdicts else 0)
+    _check(lib.mg_program_jit_source(_u8(blob), len(blob), gp, gn, bits, None, 0, C.byref(n)))
     buf = C.create_string_buffer(n.value + 1)
-    _check(lib.mg_program_jit_source(_u8(blob), len(blob), gp, gn, (1 if compile else 0) | (2 if tiled else 0), buf,
+    _check(lib.mg_program_jit_source(_u8(blob), len(blob), gp, gn, (1 if compile else 0) | bits, buf,
                                      n.value + 1, C.byref(n)))
     return buf.value.decode()
 

@@ -15,6 +15,8 @@ namespace {
 
 [[noreturn]] void err(const std::string& w) { throw SimError{w}; }
 
+constexpr int kAcc = 256;  // AGPR a<n> is register kAcc + n of the vector file
+
 #define OPS(X)                                                                                                    \
   X(s_mov_b32) X(s_mov_b64) X(s_add_u32) X(s_addc_u32) X(s_sub_u32) X(s_subb_u32) X(s_add_i32) X(s_sub_i32)       \
   X(s_mul_i32) X(s_mul_hi_u32) X(s_lshl_b32) X(s_lshr_b32) X(s_ashr_i32) X(s_lshl_b64) X(s_lshr_b64)              \
@@ -22,7 +24,7 @@ namespace {
   X(s_orn2_b64) X(s_nor_b64) X(s_xnor_b64) X(s_not_b32) X(s_not_b64) X(s_min_u32) X(s_max_u32) X(s_cselect_b32)   \
   X(s_cselect_b64) X(s_cmp_eq_u32) X(s_cmp_lg_u32) X(s_cmp_lt_u32) X(s_cmp_le_u32) X(s_cmp_gt_u32)                 \
   X(s_cmp_ge_u32) X(s_cmp_eq_u64) X(s_cmp_lg_u64) X(s_ff1_i32_b64) X(s_bcnt1_i32_b64) X(s_ff1_i32_b32)           \
-  X(s_flbit_i32_b32) X(s_brev_b32) X(s_bfe_i32) X(s_cmpk_eq_i32) X(s_cmpk_lg_i32) X(s_cmpk_eq_u32) X(s_cmpk_lg_u32) X(s_getpc_b64) X(s_movk_i32) X(s_and_saveexec_b64) X(s_or_saveexec_b64) X(s_andn2_saveexec_b64)            \
+  X(s_flbit_i32_b32) X(s_brev_b32) X(s_bfe_i32) X(s_cmpk_eq_i32) X(s_cmpk_lg_i32) X(s_cmpk_eq_u32) X(s_cmpk_lg_u32) X(s_cmpk_gt_u32) X(s_cmpk_lt_u32) X(s_getpc_b64) X(s_movk_i32) X(s_and_saveexec_b64) X(s_or_saveexec_b64) X(s_andn2_saveexec_b64)            \
   X(s_bitcmp0_b32) X(s_bitcmp1_b32) X(s_cmp_eq_i32) X(s_cmp_lg_i32) X(s_cmp_lt_i32) X(s_cmp_gt_i32)               \
   X(s_cmp_le_i32) X(s_cmp_ge_i32) X(s_min_i32) X(s_max_i32) X(s_sext_i32_i16) X(s_mul_hi_i32) X(s_bfe_u32)        \
   X(s_cbranch_scc0) X(s_cbranch_scc1) X(s_cbranch_vccz) X(s_cbranch_vccnz) X(s_cbranch_execz)                     \
@@ -41,13 +43,14 @@ namespace {
   X(v_cvt_f32_u32) X(v_rcp_iflag_f32) X(v_cvt_u32_f32) X(v_mul_f32) X(v_readlane_b32) X(v_writelane_b32)          \
   X(v_mov_b64) X(v_mbcnt_lo_u32_b32) X(v_mbcnt_hi_u32_b32) X(v_lshl_add_u64) X(v_rcp_f32) X(v_fmamk_f32)          \
   X(v_ldexp_f32) X(v_cvt_f32_ubyte0) X(v_trunc_f32) X(v_sub_f32) X(v_add_f32) X(v_fma_f32) X(v_fmac_f32)          \
-  X(v_madak_f32) X(v_cvt_f32_ubyte1) X(v_cvt_f32_ubyte2) X(v_cvt_f32_ubyte3) X(v_bcnt_u32_b32) X(v_max_i32)       \
+  X(v_madak_f32) X(v_bcnt_u32_b32) X(v_max_i32)       \
   X(v_min_i32) X(v_bfrev_b32) X(v_alignbyte_b32) X(v_xor3_b32) X(v_ashrrev_i64) X(v_mul_hi_i32) X(v_add_i32) X(v_sub_i32)                      \
-  X(global_load_dword) X(global_load_dwordx2) X(global_load_dwordx4) X(global_store_byte) X(global_store_dword)  \
+  X(v_accvgpr_write_b32) X(v_accvgpr_read_b32) X(v_accvgpr_mov_b32) X(v_bitop3_b16) X(v_pk_mov_b32) X(v_xnor_b32) X(v_mul_lo_u16) X(v_lshrrev_b16) X(v_mad_legacy_u16)                                            \
+  X(global_load_dword) X(global_load_dwordx2) X(global_load_dwordx3) X(global_load_dwordx4) X(global_store_byte) X(global_store_dword)  \
   X(global_load_lds_dword)                                                                                          \
   X(global_atomic_umin_x2) X(global_atomic_add_x2) X(flat_atomic_umin_x2) X(flat_atomic_add_x2)                  \
   X(ds_read_b32) X(ds_write_b32) X(ds_read_b64) X(ds_write_b64)                                                   \
-  X(ds_read2_b32) X(ds_read_b128) X(ds_write_b128) X(ds_min_u64) X(ds_add_u64) X(ds_add_rtn_u32) X(ds_write2_b32)
+  X(ds_read2_b32) X(ds_read_b128) X(ds_write_b128) X(ds_min_u64) X(ds_add_u64) X(ds_add_rtn_u32) X(ds_write2_b32) X(ds_add_u32)
 
 enum Op {
 #define X_ENUM(n) OP_##n,
@@ -156,6 +159,10 @@ Opd operand(const std::string& t0) {
     return o;
   }
   if (reg('v', O_V) || reg('s', O_S)) return o;
+  if (reg('a', O_V)) {  // an accumulation register: 256 + n of the vector file (v_accvgpr_* only, admit())
+    o.r += kAcc;
+    return o;
+  }
   // floating-point inline constants (their f32 bit patterns, as 32-bit operands read them)
   static const std::pair<const char*, uint32_t> kF[] = {{"0.5", 0x3F000000u},  {"-0.5", 0xBF000000u},
                                                         {"1.0", 0x3F800000u},  {"-1.0", 0xBF800000u},
@@ -177,6 +184,65 @@ Opd operand(const std::string& t0) {
     return o;
   }
   err("unknown operand '" + t + "'");
+}
+
+// modifier tokens seen on an instruction's line
+enum : unsigned { M_OFFSET = 1, M_OFFSET01 = 2, M_CACHE = 4, M_SDWA = 8, M_SDWA_DST = 16, M_BITOP3 = 32, M_OPSEL = 64 };
+
+// Fail closed: every modifier, select and encoding suffix of `ins` must be one its executor reads
+// (step() below).  What a kernel's text says and the simulator would ignore is an error here.
+void admit(const Ins& ins, unsigned seen) {
+  const int op = ins.op;
+  auto no = [&](const char* what) { err(std::string(what) + " is not modelled for this instruction: " + ins.text); };
+  const bool vmem = op >= OP_global_load_dword && op < OP_ds_read_b32;
+  const bool lds = op >= OP_ds_read_b32;
+  const bool valu = op >= OP_v_mov_b32 && op < OP_global_load_dword;
+  // the two-source ALU group whose executor applies the SDWA source selects
+  const bool alu2 = op == OP_v_add_u32 || op == OP_v_sub_u32 || op == OP_v_subrev_u32 || op == OP_v_and_b32 ||
+                    op == OP_v_or_b32 || op == OP_v_xor_b32 || op == OP_v_lshlrev_b32 || op == OP_v_lshrrev_b32 ||
+                    op == OP_v_ashrrev_i32 || op == OP_v_min_u32 || op == OP_v_max_u32 || op == OP_v_mul_u32_u24 ||
+                    op == OP_v_mul_hi_u32_u24;
+  const bool cmp32 = op >= OP_v_cmp_eq_u32 && op <= OP_v_cmp_ge_i32;
+  // encodings
+  if (ins.enc && !valu) no("an encoding suffix");
+  if (ins.enc == 3 && !(alu2 || cmp32 || op == OP_v_cndmask_b32)) no("the SDWA encoding");
+  // VOP3-only opcodes have no _e32 / _sdwa form; v_mul_lo_u32 / v_mul_hi_u32 are VOP3 on this target
+  const bool vop3_only = (op >= OP_v_bfe_u32 && op <= OP_v_bitop3_b32) || op == OP_v_lshlrev_b64 || op == OP_v_lshrrev_b64 ||
+                         op == OP_v_perm_b32 || op == OP_v_mad_u32_u24 || op == OP_v_mad_u64_u32 || op == OP_v_bfi_b32 ||
+                         op == OP_v_readlane_b32 || op == OP_v_writelane_b32 || op == OP_v_lshl_add_u64 ||
+                         op == OP_v_fma_f32 || op == OP_v_alignbyte_b32 || op == OP_v_xor3_b32 || op == OP_v_ashrrev_i64 ||
+                         op == OP_v_mul_lo_u32 || op == OP_v_mul_hi_u32 || op == OP_v_mul_hi_i32 ||
+                         op == OP_v_mad_legacy_u16 || op == OP_v_mbcnt_lo_u32_b32 || op == OP_v_mbcnt_hi_u32_b32 ||
+                         op == OP_v_bcnt_u32_b32 || op == OP_v_add_i32 || op == OP_v_sub_i32;
+  if (vop3_only && (ins.enc == 1 || ins.enc == 3)) no("a VOP1/VOP2/SDWA encoding");
+  // SDWA fields
+  if ((seen & (M_SDWA | M_SDWA_DST)) && ins.enc != 3) no("an SDWA select");
+  if ((seen & M_SDWA_DST) && cmp32) no("an SDWA destination select");
+  if (ins.dst_sel != 0 || ins.dst_unused != 0) no("an SDWA destination select other than DWORD / UNUSED_PAD");
+  // clamp: the unsigned saturation of the VOP3 subtract (the one form the compiler's kernels hold)
+  if (ins.clamp && !(op == OP_v_sub_u32 && ins.enc == 2)) no("clamp");
+  // -x / |x|: sign-bit operations on the two values v_cndmask_b32_e64 selects between
+  if (ins.neg || ins.abs) {
+    if (op != OP_v_cndmask_b32 || ins.enc != 2) no("a source modifier");
+    if ((ins.neg | ins.abs) & ~6u) no("a modifier on the destination or the select mask");
+  }
+  // AGPRs: the two moves the compiler spills VGPRs with, nothing else
+  // AGPRs: the moves the compiler spills VGPRs with, and the destination of a load
+  const bool acc = op == OP_v_accvgpr_write_b32 || op == OP_v_accvgpr_read_b32 || op == OP_v_accvgpr_mov_b32;
+  const bool is_load = op == OP_global_load_dword || op == OP_global_load_dwordx2 || op == OP_global_load_dwordx3 || op == OP_global_load_dwordx4 ||
+                       op == OP_ds_read_b32 || op == OP_ds_read_b64 || op == OP_ds_read_b128 || op == OP_ds_read2_b32;
+  for (size_t k = 0; k < ins.a.size(); k++) {
+    const bool areg = ins.a[k].k == O_V && ins.a[k].r >= kAcc;
+    const bool aslot = acc && (op == OP_v_accvgpr_mov_b32 || k == (op == OP_v_accvgpr_write_b32 ? 0u : 1u));
+    if (areg && !(aslot && ins.a[k].n == 1) && !(is_load && k == 0)) no("an AGPR operand");
+    if (aslot && !areg) no("a VGPR in the AGPR slot");
+  }
+  if ((seen & M_OFFSET) && !(vmem || lds)) no("offset:");
+  if ((seen & M_OFFSET) && (op == OP_ds_read2_b32 || op == OP_ds_write2_b32)) no("offset: (offset0: / offset1: here)");
+  if ((seen & M_OFFSET01) && op != OP_ds_read2_b32 && op != OP_ds_write2_b32) no("offset0: / offset1:");
+  if ((seen & M_CACHE) && !vmem) no("a cache policy bit");
+  if ((seen & M_BITOP3) && op != OP_v_bitop3_b32 && op != OP_v_bitop3_b16) no("bitop3:");
+  if ((seen & M_OPSEL) && op != OP_v_pk_mov_b32) no("op_sel");
 }
 
 }  // namespace
@@ -285,6 +351,22 @@ Module parse(const std::string& text) {
       m.code.push_back(ins);
       continue;
     }
+    // op_sel:[a,b,..] holds commas: taken out before the operands are split
+    unsigned seen = 0;
+    {
+      const size_t os = rest.find("op_sel:[");
+      if (os != std::string::npos) {
+        const size_t cl = rest.find(']', os);
+        if (cl == std::string::npos) err("bad op_sel " + ins.text);
+        int k = 0;
+        for (size_t q = os + 8; q < cl; q++) {
+          if (rest[q] == '0' || rest[q] == '1') ins.op_sel |= (unsigned)(rest[q] - '0') << k++;
+          else if (rest[q] != ',') err("bad op_sel " + ins.text);
+        }
+        rest = rest.substr(0, os) + rest.substr(cl + 1);
+        seen |= M_OPSEL;
+      }
+    }
     // operands separated by commas; modifiers (offset:N, sc0/sc1/nt, sdwa selects) after the last
     std::vector<std::string> parts;
     {
@@ -305,6 +387,7 @@ Module parse(const std::string& text) {
       ls >> first;
       std::vector<std::string> mods;
       while (ls >> tok) mods.push_back(tok);
+      // a source modifier spelt with blanks ("- v1") is not one of the forms below: refused as an operand
       // a lone modifier list after an operand ("s[4:5] offset:8")
       parts.back() = first;
       for (const std::string& md : mods) {
@@ -312,33 +395,63 @@ Module parse(const std::string& text) {
           int64_t v;
           if (!parse_int(md.substr(7), v)) err("bad offset " + ins.text);
           ins.offset = v;
+          seen |= M_OFFSET;
         } else if (md == "sc0" || md == "sc1" || md == "nt") {
           // cache policy bits: no effect on a single-device simulation
+          seen |= M_CACHE;
         } else if (md.rfind("offset0:", 0) == 0 || md.rfind("offset1:", 0) == 0) {
           int64_t v;
           if (!parse_int(md.substr(8), v)) err("bad offset " + ins.text);
           (md[6] == '0' ? ins.offset0 : ins.offset1) = (int)v;
-        } else if (md.rfind("src0_sel:", 0) == 0 || md.rfind("src1_sel:", 0) == 0) {
-          const std::string s = md.substr(9);
+          seen |= M_OFFSET01;
+        } else if (md.rfind("src0_sel:", 0) == 0 || md.rfind("src1_sel:", 0) == 0 || md.rfind("dst_sel:", 0) == 0) {
+          const std::string s = md.substr(md.find(':') + 1);
           static const char* kSel[] = {"DWORD", "WORD_0", "WORD_1", "BYTE_0", "BYTE_1", "BYTE_2", "BYTE_3"};
           int k = -1;
           for (int q = 0; q < 7; q++)
             if (s == kSel[q]) k = q;
           if (k < 0) err("unsupported sdwa select " + ins.text);
-          ins.sdwa_sel[md[3] - '0'] = k;
-          if (md[3] == '1' && k == 2) ins.sdwa_src1_word1 = 1;
+          if (md[0] == 'd') ins.dst_sel = k;
+          else ins.sdwa_sel[md[3] - '0'] = k;
+          seen |= md[0] == 'd' ? M_SDWA_DST : M_SDWA;
+        } else if (md.rfind("dst_unused:", 0) == 0) {
+          const std::string s = md.substr(11);
+          ins.dst_unused = s == "UNUSED_PAD" ? 0 : s == "UNUSED_SEXT" ? 1 : s == "UNUSED_PRESERVE" ? 2 : -1;
+          if (ins.dst_unused < 0) err("unsupported sdwa dst_unused " + ins.text);
+          seen |= M_SDWA_DST;
         } else if (md.rfind("bitop3:", 0) == 0) {
           int64_t v;
           if (!parse_int(md.substr(7), v) || v < 0 || v > 255) err("bad bitop3 table " + ins.text);
           ins.bitop3 = (int)v;
-        } else if (md == "dst_sel:DWORD" || md == "dst_unused:UNUSED_PAD" || md == "src0_sel:DWORD") {
+          seen |= M_BITOP3;
+        } else if (md == "clamp") {
+          ins.clamp = true;
         } else {
           err("unsupported modifier '" + md + "' in " + ins.text);
         }
       }
     }
-    for (const std::string& p : parts) ins.a.push_back(operand(p));
+    for (const std::string& p0 : parts) {
+      // VOP3 source modifiers: -x, |x|, -|x| on a register
+      std::string p = trim(p0);
+      const size_t k = ins.a.size();
+      bool ng = false, ab = false;
+      if (p.size() > 1 && p[0] == '-' && !isdigit((unsigned char)p[1])) {
+        ng = true;
+        p = p.substr(1);
+      }
+      if (p.size() > 2 && p[0] == '|' && p.back() == '|') {
+        ab = true;
+        p = p.substr(1, p.size() - 2);
+      }
+      if ((ng || ab) && k >= 8) err("too many operands " + ins.text);
+      if (ng) ins.neg |= 1u << k;
+      if (ab) ins.abs |= 1u << k;
+      ins.a.push_back(operand(p));
+      if ((ng || ab) && ins.a.back().k != O_V && ins.a.back().k != O_S) err("source modifier on a constant " + ins.text);
+    }
     ins.enc = enc;
+    admit(ins, seen);
     m.code.push_back(ins);
   }
   for (auto& f : fix) {
@@ -394,12 +507,14 @@ struct Pend {
 };
 
 struct Wave {
-  uint32_t v[256][64];
-  bool vinit[256];
+  uint32_t v[512][64];
+  bool vinit[512];
+  uint64_t vundef[512];  // lanes holding the spill of a never-written SGPR
+  uint64_t vlane[512];  // lanes of each VGPR some instruction wrote (v_writelane_b32 / v_readlane_b32)
   uint32_t s[kNS];
   bool sinit[kNS];
   int64_t sw[kNS];  // slot of the last VALU write
-  int vpend[256];
+  int vpend[512];
   int spend[kNS];
   std::deque<Pend> vm, lgkm;
   uint64_t exec = ~0ull;
@@ -430,7 +545,7 @@ struct Ctx {
 
 // --- register access with the checks ---------------------------------------------------------
 inline void chk_v_read(const Wave& w, const Ctx& c, const Ins& in, int r) {
-  if (r < 0 || r > 255) fail(w, c, in, "VGPR out of range");
+  if (r < 0 || r > 511) fail(w, c, in, "VGPR out of range");
   if (w.vpend[r]) fail(w, c, in, "read of v" + std::to_string(r) + " with a load in flight");
   if (!w.vinit[r]) fail(w, c, in, "read of v" + std::to_string(r) + " before any write");
 }
@@ -440,7 +555,7 @@ inline void chk_s_read(const Wave& w, const Ctx& c, const Ins& in, int r) {
   if (!w.sinit[r]) fail(w, c, in, "read of s" + std::to_string(r) + " before any write");
 }
 inline void chk_v_write(const Wave& w, const Ctx& c, const Ins& in, int r) {
-  if (r < 0 || r > 255) fail(w, c, in, "VGPR out of range");
+  if (r < 0 || r > 511) fail(w, c, in, "VGPR out of range");
   if (w.vpend[r]) fail(w, c, in, "write of v" + std::to_string(r) + " with a load into it in flight");
 }
 inline void chk_s_write(const Wave& w, const Ctx& c, const Ins& in, int r) {
@@ -464,10 +579,16 @@ uint64_t sread64(Wave& w, const Ctx& c, const Ins& in, const Opd& o) {
       chk_s_read(w, c, in, o.r + 1);
       return (uint64_t)w.s[o.r] | ((uint64_t)w.s[o.r + 1] << 32);
     case O_IMM:
-      // a 32-bit literal below 2^31 reads the same zero- or sign-extended (the only kind the tier
-      // emits none of; the O3 tier's compiler does, e.g. s_mov_b64 s[4:5], 0x248)
-      if (!o.inl && (o.imm >> 31) != 0) fail(w, c, in, "32-bit literal with bit 31 set in a 64-bit scalar operand");
-      return (uint64_t)(int64_t)(int32_t)(uint32_t)o.imm;
+      // an inline constant is sign-extended; a 32-bit literal is zero-extended: the compiler turns a
+      // 64-bit move into s_mov_b64 with a literal only when the value's upper word is zero
+      // (s_mov_b64 s[0:1], 0xffffffff is the low-word mask; all ones is the inline -1), and the
+      // disassembler prints the literal unsigned.  The assembler also takes a negative literal and
+      // encodes it to the same 32 bits (llvm-mc: -14382316 and 0xff248b14 are one encoding), so a
+      // negative one in a kernel's text does not mean what it says: an error.
+      if (o.inl) return (uint64_t)(int64_t)(int32_t)(uint32_t)o.imm;
+      if ((int64_t)o.imm < 0) fail(w, c, in, "negative 32-bit literal in a 64-bit scalar operand (it reads zero-extended)");
+      if (o.imm >> 32) fail(w, c, in, "literal wider than 32 bits");
+      return o.imm;
     case O_EXEC: return w.exec;
     default: fail(w, c, in, "bad scalar operand");
   }
@@ -591,6 +712,8 @@ uint32_t* vdst(Wave& w, const Ctx& c, const Ins& in, const Opd& o, int k = 0) {
   if (o.k != O_V) fail(w, c, in, "VALU destination is not a VGPR");
   chk_v_write(w, c, in, o.r + k);
   w.vinit[o.r + k] = true;
+  w.vlane[o.r + k] |= w.exec;
+  w.vundef[o.r + k] &= ~w.exec;
   return w.v[o.r + k];
 }
 
@@ -619,6 +742,12 @@ uint32_t sdwa(uint32_t x, int sel) {
     case 2: return x >> 16;
     default: return (x >> (8 * (sel - 3))) & 0xFFu;
   }
+}
+// the VOP3 source modifiers of operand k: |x| clears the sign bit, then -x flips it
+inline uint32_t fmods(const Ins& in, int k, uint32_t x) {
+  if (in.abs >> k & 1) x &= 0x7FFFFFFFu;
+  if (in.neg >> k & 1) x ^= 0x80000000u;
+  return x;
 }
 float f32(uint32_t x) {
   float f;
@@ -769,6 +898,13 @@ bool step(Wave& w, Ctx& c) {
         }
         w.scc = v != 0;
         swrite(w, c, in, a[0], (uint32_t)v);
+        break;
+      }
+      case OP_s_cmpk_gt_u32: case OP_s_cmpk_lt_u32: {
+        need(2);
+        if (a[1].k != O_IMM || a[1].imm > 0xFFFFu) fail(w, c, in, "SOPK immediate");
+        const uint32_t x = sread(w, c, in, a[0]), k16 = (uint32_t)a[1].imm;
+        w.scc = op == OP_s_cmpk_gt_u32 ? x > k16 : x < k16;
         break;
       }
       case OP_s_cmpk_eq_i32: case OP_s_cmpk_lg_i32: case OP_s_cmpk_eq_u32: case OP_s_cmpk_lg_u32: {
@@ -1022,6 +1158,20 @@ bool step(Wave& w, Ctx& c) {
           memcpy(p, &cur, 8);
         }
         w.lgkm.push_back(Pend{});
+      } else if (op == OP_ds_add_u32) {
+        need(2);
+        ValuCheck vc;
+        const Src ad = vsrc(w, c, in, a[0], false, vc, true);
+        const Src dv = vsrc(w, c, in, a[1], false, vc, true);
+        for (int l = 0; l < 64; l++) {
+          if (!(w.exec >> l & 1)) continue;
+          uint8_t* p = lds_at(ad.lo(l) + (uint32_t)in.offset, 4);
+          uint32_t cur;
+          memcpy(&cur, p, 4);
+          cur += dv.lo(l);
+          memcpy(p, &cur, 4);
+        }
+        w.lgkm.push_back(Pend{});
       } else if (op == OP_ds_add_rtn_u32) {
         need(3);
         ValuCheck vc;
@@ -1127,11 +1277,25 @@ bool step(Wave& w, Ctx& c) {
     if (in.offset < -4096 || in.offset > 4095) fail(w, c, in, "global offset outside 13 signed bits");
     auto addr = [&](int l) -> uint64_t { return (off ? av.v64(l) : sb + av.lo(l)) + (uint64_t)in.offset; };
     if (load) {
-      const int nw = op == OP_global_load_dword ? 1 : op == OP_global_load_dwordx2 ? 2 : 4;
+      const int nw = op == OP_global_load_dword ? 1 : op == OP_global_load_dwordx2 ? 2 : op == OP_global_load_dwordx3 ? 3 : 4;
       if (a[0].k != O_V || a[0].n != nw) fail(w, c, in, "load destination width");
       Pend pd;
       std::vector<uint32_t*> ds;
-      for (int q = 0; q < nw; q++) ds.push_back(vdst(w, c, in, a[0], q));
+      // a load into a register an earlier global load still targets is in order (loads of one counter
+      // return in issue order: the later value stands); one an LDS load still targets is not
+      for (int q = 0; q < nw; q++) {
+        const int r = a[0].r + q;
+        int in_vm = 0;
+        for (const Pend& pd0 : w.vm) in_vm += (int)std::count(pd0.v.begin(), pd0.v.end(), r);
+        if (r >= 0 && r < 2 * kAcc && w.vpend[r] && in_vm == w.vpend[r]) {
+          w.vinit[r] = true;
+          w.vlane[r] |= w.exec;
+          w.vundef[r] &= ~w.exec;
+          ds.push_back(w.v[r]);
+        } else {
+          ds.push_back(vdst(w, c, in, a[0], q));
+        }
+      }
       for (int l = 0; l < 64; l++) {
         if (!(w.exec >> l & 1)) continue;
         const uint8_t* p = c.mem.at(addr(l), 4u * nw);
@@ -1185,8 +1349,9 @@ bool step(Wave& w, Ctx& c) {
     if (enc == 1 && o.k != O_V) fail(w, c, in, "VOP2/VOPC src1 must be a VGPR");
   };
   switch (op) {
-    case OP_v_mov_b32: {
+    case OP_v_mov_b32: case OP_v_accvgpr_write_b32: case OP_v_accvgpr_read_b32: case OP_v_accvgpr_mov_b32: {
       need(2);
+      if (op != OP_v_mov_b32 && a[1].k != O_V && !(a[1].k == O_IMM && a[1].inl)) fail(w, c, in, "accvgpr source");
       const Src s = vsrc(w, c, in, a[1], false, vc, vop3);
       uint32_t* d = vdst(w, c, in, a[0]);
       lanes([&](int l) { d[l] = s.lo(l); });
@@ -1205,7 +1370,8 @@ bool step(Wave& w, Ctx& c) {
     }
     case OP_v_add_u32: case OP_v_sub_u32: case OP_v_subrev_u32: case OP_v_and_b32: case OP_v_or_b32:
     case OP_v_xor_b32: case OP_v_lshlrev_b32: case OP_v_lshrrev_b32: case OP_v_ashrrev_i32: case OP_v_min_u32:
-    case OP_v_max_u32: case OP_v_mul_u32_u24: case OP_v_mul_hi_u32_u24: case OP_v_mul_lo_u32: case OP_v_mul_hi_u32: {
+    case OP_v_max_u32: case OP_v_mul_u32_u24: case OP_v_mul_hi_u32_u24: case OP_v_mul_lo_u32: case OP_v_mul_hi_u32:
+    case OP_v_xnor_b32: case OP_v_mul_lo_u16: case OP_v_lshrrev_b16: {
       need(3);
       e32_src1(a[2]);
       const Src x = vsrc(w, c, in, a[1], false, vc, vop3), y = vsrc(w, c, in, a[2], false, vc, vop3);
@@ -1216,8 +1382,12 @@ bool step(Wave& w, Ctx& c) {
         uint32_t r = 0;
         switch (op) {
           case OP_v_add_u32: r = p + q; break;
-          case OP_v_sub_u32: r = p - q; break;
+          case OP_v_sub_u32: r = p - q; if (in.clamp && q > p) r = 0; break;  // clamp: unsigned saturation (VOP3 only)
           case OP_v_subrev_u32: r = q - p; break;
+          case OP_v_xnor_b32: r = ~(p ^ q); break;
+          // 16-bit VOP2: the low halves; the destination's high half is written as zero on this target
+          case OP_v_mul_lo_u16: r = ((p & 0xFFFFu) * (q & 0xFFFFu)) & 0xFFFFu; break;
+          case OP_v_lshrrev_b16: r = (q & 0xFFFFu) >> (p & 15); break;
           case OP_v_and_b32: r = p & q; break;
           case OP_v_or_b32: r = p | q; break;
           case OP_v_xor_b32: r = p ^ q; break;
@@ -1241,7 +1411,7 @@ bool step(Wave& w, Ctx& c) {
       const Src x = vsrc(w, c, in, a[1], false, vc, vop3);
       uint32_t* d = vdst(w, c, in, a[0]);
       lanes([&](int l) {
-        const uint32_t p = enc == 3 ? sdwa(x.lo(l), in.sdwa_sel[0]) : x.lo(l);
+        const uint32_t p = x.lo(l);  // (no SDWA form: admit())
         uint32_t r;
         float f;
         switch (op) {
@@ -1312,14 +1482,20 @@ bool step(Wave& w, Ctx& c) {
       e32_src1(a[2]);
       const Src x = vsrc(w, c, in, a[1], false, vc, vop3), y = vsrc(w, c, in, a[2], false, vc, vop3);
       uint64_t m;
-      if (enc == 1) {
-        if (!(a[3].k == O_S && a[3].r == 106)) fail(w, c, in, "e32 select must be vcc");
+      if (enc == 1 || enc == 3) {
+        if (!(a[3].k == O_S && a[3].r == 106)) fail(w, c, in, "e32 / SDWA select must be vcc");
         m = vcc_read(w, c, in, vc);
       } else {
         m = mask_read(w, c, in, a[3], vc);
       }
       uint32_t* d = vdst(w, c, in, a[0]);
-      lanes([&](int l) { d[l] = (m >> l & 1) ? y.lo(l) : x.lo(l); });
+      lanes([&](int l) {
+        if (enc == 3) {
+          d[l] = (m >> l & 1) ? sdwa(y.lo(l), in.sdwa_sel[1]) : sdwa(x.lo(l), in.sdwa_sel[0]);
+        } else {
+          d[l] = (m >> l & 1) ? fmods(in, 2, y.lo(l)) : fmods(in, 1, x.lo(l));
+        }
+      });
       break;
     }
     case OP_v_cmp_eq_u32: case OP_v_cmp_ne_u32: case OP_v_cmp_lt_u32: case OP_v_cmp_le_u32: case OP_v_cmp_gt_u32:
@@ -1330,6 +1506,7 @@ bool step(Wave& w, Ctx& c) {
       e32_src1(a[2]);
       if (enc == 1 && !(a[0].k == O_S && a[0].r == 106 && a[0].n == 2)) fail(w, c, in, "e32 compare must write vcc");
       const bool wide = op >= OP_v_cmp_eq_u64;
+      if (wide && enc == 3) fail(w, c, in, "64-bit compare in the SDWA encoding");
       const Src x = vsrc(w, c, in, a[1], wide, vc, vop3), y = vsrc(w, c, in, a[2], wide, vc, vop3);
       uint64_t m = 0;
       lanes([&](int l) {
@@ -1345,7 +1522,9 @@ bool step(Wave& w, Ctx& c) {
             default: r = p >= q; break;
           }
         } else if (op >= OP_v_cmp_eq_i32) {
-          const int32_t p = (int32_t)x.lo(l), q = (int32_t)y.lo(l);
+          // SDWA: the selected byte or word, zero-extended (no sext() modifier is parsed), then compared
+          const int32_t p = (int32_t)(enc == 3 ? sdwa(x.lo(l), in.sdwa_sel[0]) : x.lo(l)),
+                        q = (int32_t)(enc == 3 ? sdwa(y.lo(l), in.sdwa_sel[1]) : y.lo(l));
           switch (op) {
             case OP_v_cmp_eq_i32: r = p == q; break;
             case OP_v_cmp_ne_i32: r = p != q; break;
@@ -1355,7 +1534,8 @@ bool step(Wave& w, Ctx& c) {
             default: r = p >= q; break;
           }
         } else {
-          const uint32_t p = x.lo(l), q = y.lo(l);
+          const uint32_t p = enc == 3 ? sdwa(x.lo(l), in.sdwa_sel[0]) : x.lo(l),
+                         q = enc == 3 ? sdwa(y.lo(l), in.sdwa_sel[1]) : y.lo(l);
           switch (op) {
             case OP_v_cmp_eq_u32: r = p == q; break;
             case OP_v_cmp_ne_u32: r = p != q; break;
@@ -1372,7 +1552,8 @@ bool step(Wave& w, Ctx& c) {
     }
     case OP_v_bfe_u32: case OP_v_bfe_i32: case OP_v_alignbit_b32: case OP_v_lshl_or_b32: case OP_v_add3_u32:
     case OP_v_or3_b32: case OP_v_xad_u32: case OP_v_and_or_b32: case OP_v_lshl_add_u32: case OP_v_add_lshl_u32:
-    case OP_v_perm_b32: case OP_v_mad_u32_u24: case OP_v_bfi_b32: case OP_v_alignbyte_b32: case OP_v_xor3_b32: {
+    case OP_v_perm_b32: case OP_v_mad_u32_u24: case OP_v_bfi_b32: case OP_v_alignbyte_b32: case OP_v_xor3_b32:
+    case OP_v_mad_legacy_u16: {
       need(4);
       const Src x = vsrc(w, c, in, a[1], false, vc, true), y = vsrc(w, c, in, a[2], false, vc, true),
                 z = vsrc(w, c, in, a[3], false, vc, true);
@@ -1408,6 +1589,8 @@ bool step(Wave& w, Ctx& c) {
           case OP_v_bfi_b32: r = (p & q) | (~p & s); break;
           case OP_v_alignbyte_b32: r = (uint32_t)((((uint64_t)p << 32) | q) >> (8 * (s & 3))); break;
           case OP_v_xor3_b32: r = p ^ q ^ s; break;
+          // the 16-bit multiply-add that writes the destination's high half as zero (op_sel is refused)
+          case OP_v_mad_legacy_u16: r = ((p & 0xFFFFu) * (q & 0xFFFFu) + (s & 0xFFFFu)) & 0xFFFFu; break;
           default: {  // v_perm_b32: byte selects from {p, q}
             const uint64_t cat = ((uint64_t)p << 32) | q;
             for (int b = 0; b < 4; b++) {
@@ -1437,6 +1620,36 @@ bool step(Wave& w, Ctx& c) {
       lanes([&](int l) { d[l] = bitop3(x.lo(l), y.lo(l), z.lo(l), t); });
       break;
     }
+    case OP_v_bitop3_b16: {
+      // the low halves; without op_sel the result goes to the destination's low half and the high
+      // half is kept (an op_sel VOP3: the unselected half of the destination is preserved)
+      need(4);
+      const Src x = vsrc(w, c, in, a[1], false, vc, true), y = vsrc(w, c, in, a[2], false, vc, true),
+                z = vsrc(w, c, in, a[3], false, vc, true);
+      if (in.bitop3 < 0) fail(w, c, in, "bitop3 without a table");
+      const uint32_t t = (uint32_t)in.bitop3;
+      uint32_t* d = vdst(w, c, in, a[0]);
+      lanes([&](int l) { d[l] = (d[l] & 0xFFFF0000u) | (bitop3(x.lo(l), y.lo(l), z.lo(l), t) & 0xFFFFu); });
+      break;
+    }
+    case OP_v_pk_mov_b32: {
+      // D.lo = the dword of S0 that op_sel[0] names, D.hi = the dword of S1 that op_sel[1] names
+      need(3);
+      const Src x = vsrc(w, c, in, a[1], true, vc, true), y = vsrc(w, c, in, a[2], true, vc, true);
+      if (a[0].k != O_V || a[0].n != 2) fail(w, c, in, "64-bit destination");
+      uint32_t lo[64], hi[64];  // the destination may overlap a source
+      for (int l = 0; l < 64; l++) {
+        lo[l] = (uint32_t)(x.v64(l) >> (in.op_sel & 1 ? 32 : 0));
+        hi[l] = (uint32_t)(y.v64(l) >> (in.op_sel & 2 ? 32 : 0));
+      }
+      uint32_t* d0 = vdst(w, c, in, a[0], 0);
+      uint32_t* d1 = vdst(w, c, in, a[0], 1);
+      lanes([&](int l) {
+        d0[l] = lo[l];
+        d1[l] = hi[l];
+      });
+      break;
+    }
     case OP_v_lshlrev_b64: case OP_v_lshrrev_b64: {
       need(3);
       const Src x = vsrc(w, c, in, a[1], false, vc, true), y = vsrc(w, c, in, a[2], true, vc, true);
@@ -1455,38 +1668,69 @@ bool step(Wave& w, Ctx& c) {
     case OP_v_mad_u64_u32: {
       // v_mad_u64_u32 v[d:d+1], s[c:c+1], a, b, v[e:e+1]: d = a * b + e, carry-out to the pair
       need(5);
+      // The compiler adds a 32-bit value through this instruction with the addend's high register
+      // never written (only the low half of the result is used): the low half of the result is then
+      // defined, and the high half and the carry mask count as never written, so a later use of
+      // either is the error.
+      const bool hi_undef = a[4].k == O_V && a[4].n == 2 && a[4].r + 1 < 2 * kAcc && !w.vinit[a[4].r + 1] &&
+                            !w.vpend[a[4].r + 1];
+      Opd lo_only = a[4];
+      lo_only.n = 1;
       const Src x = vsrc(w, c, in, a[2], false, vc, true), y = vsrc(w, c, in, a[3], false, vc, true),
-                z = vsrc(w, c, in, a[4], true, vc, true);
+                z = hi_undef ? vsrc(w, c, in, lo_only, false, vc, true) : vsrc(w, c, in, a[4], true, vc, true);
+      if (a[0].k != O_V || a[0].n != 2) fail(w, c, in, "64-bit destination");
       uint32_t* d0 = vdst(w, c, in, a[0], 0);
       uint32_t* d1 = vdst(w, c, in, a[0], 1);
       uint64_t m = 0;
       lanes([&](int l) {
-        const unsigned __int128 t = (unsigned __int128)x.lo(l) * y.lo(l) + z.v64(l);
+        const unsigned __int128 t = (unsigned __int128)x.lo(l) * y.lo(l) + (hi_undef ? (uint64_t)z.lo(l) : z.v64(l));
         d0[l] = (uint32_t)t;
         d1[l] = (uint32_t)(t >> 32);
         m |= (uint64_t)(t >> 64 & 1) << l;
       });
       mask_write(w, c, in, a[1], m);
+      if (hi_undef) {
+        w.vinit[a[0].r + 1] = false;
+        w.vlane[a[0].r + 1] = 0;
+        w.sinit[a[1].r] = w.sinit[a[1].r + 1] = false;
+      }
       break;
     }
     case OP_v_readlane_b32: {
+      // per lane: the lane read must have been written.  The one value that may travel unwritten is
+      // an SGPR the compiler spilt before anything defined it (a lane v_writelane_b32 filled from a
+      // never-written SGPR): the destination then counts as never written, and its first use is
+      // the error (chk_s_read), not the reload.
       need(3);
-      const Src x = vsrc(w, c, in, a[1], false, vc, true);
+      if (a[1].k != O_V) fail(w, c, in, "readlane source");
+      if (a[1].r < 0 || a[1].r > 255) fail(w, c, in, "VGPR out of range");
+      if (w.vpend[a[1].r]) fail(w, c, in, "read of v" + std::to_string(a[1].r) + " with a load in flight");
       const uint32_t lane = sread(w, c, in, a[2]) & 63;
       if (a[0].k != O_S) fail(w, c, in, "readlane destination");
       chk_s_write(w, c, in, a[0].r);
-      w.s[a[0].r] = x.lo((int)lane);
-      w.sinit[a[0].r] = true;
+      const bool written = w.vlane[a[1].r] >> lane & 1;
+      if (!written && !(w.vundef[a[1].r] >> lane & 1))
+        fail(w, c, in, "read of v" + std::to_string(a[1].r) + " lane " + std::to_string(lane) + " before any write");
+      w.s[a[0].r] = w.v[a[1].r][lane];
+      w.sinit[a[0].r] = written;
       w.sw[a[0].r] = w.slot;
       break;
     }
     case OP_v_writelane_b32: {
       need(3);
-      const Src x = vsrc(w, c, in, a[1], false, vc, true);
       const uint32_t lane = sread(w, c, in, a[2]) & 63;
       if (a[0].k != O_V) fail(w, c, in, "writelane destination");
       chk_v_write(w, c, in, a[0].r);
+      if (a[1].k == O_S && a[1].r >= 0 && a[1].r < kNS && !w.sinit[a[1].r] && !w.spend[a[1].r]) {
+        // a spill of an SGPR nothing has written yet: the lane holds no value (see v_readlane_b32)
+        w.vlane[a[0].r] &= ~(1ull << lane);
+        w.vundef[a[0].r] |= 1ull << lane;
+        break;
+      }
+      const Src x = vsrc(w, c, in, a[1], false, vc, true);
       w.v[a[0].r][lane] = x.lo((int)lane);
+      w.vlane[a[0].r] |= 1ull << lane;
+      w.vundef[a[0].r] &= ~(1ull << lane);
       break;
     }
     case OP_v_mov_b64: {
@@ -1563,8 +1807,7 @@ bool step(Wave& w, Ctx& c) {
       });
       break;
     }
-    case OP_v_rcp_f32: case OP_v_trunc_f32: case OP_v_cvt_f32_ubyte0: case OP_v_cvt_f32_ubyte1:
-    case OP_v_cvt_f32_ubyte2: case OP_v_cvt_f32_ubyte3: {
+    case OP_v_rcp_f32: case OP_v_trunc_f32: case OP_v_cvt_f32_ubyte0: {
       need(2);
       const Src x = vsrc(w, c, in, a[1], false, vc, vop3);
       uint32_t* d = vdst(w, c, in, a[0]);
@@ -1573,7 +1816,9 @@ bool step(Wave& w, Ctx& c) {
         switch (op) {
           case OP_v_rcp_f32: d[l] = u32f(1.0f / f32(p)); break;
           case OP_v_trunc_f32: d[l] = u32f(std::trunc(f32(p))); break;
-          default: d[l] = u32f((float)((p >> (8 * (op - OP_v_cvt_f32_ubyte0))) & 0xFFu)); break;
+          // (v_cvt_f32_ubyte1..3 were listed and read the wrong byte; no kernel of either tier holds one:
+          // unknown instructions now)
+          default: d[l] = u32f((float)(p & 0xFFu)); break;
         }
       });
       break;
@@ -1653,6 +1898,8 @@ void launch(const Module& m, const std::string& kernel, Memory& mem, uint64_t ke
     for (int q = 0; q < 4; q++) {
       Wave& w = waves[q];
       memset(w.vinit, 0, sizeof w.vinit);
+      memset(w.vlane, 0, sizeof w.vlane);
+      memset(w.vundef, 0, sizeof w.vundef);
       memset(w.sinit, 0, sizeof w.sinit);
       memset(w.vpend, 0, sizeof w.vpend);
       memset(w.spend, 0, sizeof w.spend);
@@ -1667,6 +1914,7 @@ void launch(const Module& m, const std::string& kernel, Memory& mem, uint64_t ke
       w.id = q;
       for (int l = 0; l < 64; l++) w.v[0][l] = (uint32_t)(64 * q + l);
       w.vinit[0] = true;
+      w.vlane[0] = ~0ull;
       w.s[0] = (uint32_t)kernarg;
       w.s[1] = (uint32_t)(kernarg >> 32);
       w.s[2] = b;

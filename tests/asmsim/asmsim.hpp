@@ -14,7 +14,15 @@
 //   * the constant bus: one SGPR or literal per VALU instruction (implicit VCC included), no
 //     32-bit literal in a VOP3 encoding;
 //   * an access outside every buffer, or outside the kernel's LDS allocation;
-//   * a read of a VGPR no instruction wrote in this wave;
+//   * a read of a VGPR no instruction wrote in this wave (v_writelane_b32 / v_readlane_b32 per lane:
+//     a lane is read only after it was written; an SGPR that was never written travels through a
+//     spill lane as unwritten, and its first use after the reload is the error);
+//   * a 32-bit literal in a 64-bit scalar operand reads zero-extended (what the hardware does and the
+//     compiler relies on: s_mov_b64 s[0:1], 0xffffffff is the low-word mask, -1 is the inline
+//     constant); a negative literal there, which the assembler encodes to the same 32 bits, is an error;
+//   * fail-closed parsing: a modifier, encoding suffix or select (SDWA selects, clamp, -x / |x|,
+//     op_sel, DPP controls, offsets, cache bits) on an opcode whose executor does not model it is an
+//     error at parse time, never a silent run;
 //   * a kernel that runs more than a step budget (a wave that never exits).
 #pragma once
 #include <cstdint>
@@ -42,8 +50,12 @@ struct Ins {
   std::vector<Opd> a;
   int64_t offset = 0;   // offset:N
   int vmcnt = -1, lgkmcnt = -1;  // s_waitcnt
-  int sdwa_src1_word1 = 0;
   int sdwa_sel[2] = {0, 0};  // SDWA source selects: 0 DWORD, 1 WORD_0, 2 WORD_1, 3..6 BYTE_0..3
+  int dst_sel = 0;           // SDWA destination select (same numbering): DWORD only, the rest is refused
+  int dst_unused = 0;        // SDWA dst_unused: 0 UNUSED_PAD (1 UNUSED_SEXT, 2 UNUSED_PRESERVE: refused)
+  unsigned op_sel = 0;       // op_sel:[..] bits (v_pk_mov_b32)
+  bool clamp = false;        // VOP3 clamp (v_sub_u32: unsigned saturation)
+  uint8_t neg = 0, abs = 0;  // VOP3 source modifiers -x / |x|, bit k: operand k (v_cndmask_b32: sign-bit operations)
   int offset0 = 0, offset1 = 0;  // ds_read2 / ds_write2 (dwords)
   int enc = 0;          // 0 VOP3-only / none, 1 _e32, 2 _e64, 3 _sdwa
   int bitop3 = -1;      // v_bitop3_b32's table

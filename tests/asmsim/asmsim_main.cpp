@@ -7,6 +7,8 @@
 //           and hit count (plus the early-exit first hit, and the hit lowered into a peer's word);
 //   kind 1/2: mgj_eval (row-major / tiled SoA) verdicts on random coordinate rows (masked to each
 //           coordinate's width), count candidates.
+// With ASMSIM_O3_DUMP / ASMSIM_SEARCH_SOURCE_DIR (check_search) the kind 0 records judge the O3 tier's
+// compiled kernels instead: this driver compiles them and runs their disassembly (tests/test_o3_sim_cpu.py).
 // Built by tests/test_asm_sim.py with g++ (optionally -fsanitize=address,undefined).
 //
 // stdin records: u32 kind | u32 prog_len | prog | u32 gen_words (0xFFFFFFFF none) | gen words |
@@ -102,6 +104,47 @@ std::string check_search(uint64_t rec, const std::vector<uint8_t>& prog, const s
   // ASMSIM_SEARCH_SOURCE=<file>: run this kernel text instead of the first tier's (the O3 tier's
   // code object through tools/o3dis.py: its instruction counts, LDS bank conflicts and verdicts)
   const char* ext = getenv("ASMSIM_SEARCH_SOURCE");
+  // The O3 tier's own kernels, record by record (tests/test_o3_sim_cpu.py), in two passes of this driver:
+  //   ASMSIM_O3_DUMP=<dir>: compile the record's search + gen kernels as the engine does (jit_source with
+  //     JIT_SEARCH | JIT_GEN, jit_compile_local: this tree's jit.cpp, the options of this process's
+  //     environment), write <dir>/<rec>.hip and <dir>/<rec>.co, print the code object's private segment, stop;
+  //   ASMSIM_SEARCH_SOURCE_DIR=<dir>: run <dir>/<rec>.s (tools/o3dis.py's text of that code object).
+  const char* o3dump = getenv("ASMSIM_O3_DUMP");
+  const char* extdir = getenv("ASMSIM_SEARCH_SOURCE_DIR");
+  std::string ext_path;
+  if (extdir) {
+    ext_path = std::string(extdir) + "/" + std::to_string(rec) + ".s";
+    ext = ext_path.c_str();
+  }
+  if (o3dump) {
+#ifdef ASMSIM_ASSEMBLER
+    const std::string hip = jit_source(sp, &specs, &consts, JIT_SEARCH | JIT_GEN);
+    std::vector<char> code;
+    std::string log;
+    if (jit_compile_local(hip, code, log)) {
+      C.asmerror++;
+      return "O3 compile: " + log.substr(0, 2000);
+    }
+    CodeObjectInfo ci;
+    if (code_object_info(code.data(), code.size(), ci, err)) {
+      C.asmerror++;
+      return "O3 code object: " + err;
+    }
+    const std::string base = std::string(o3dump) + "/" + std::to_string(rec);
+    for (int k = 0; k < 2; k++) {
+      FILE* f = fopen((base + (k ? ".co" : ".hip")).c_str(), "wb");
+      if (!f) return "cannot write " + base;
+      if (k) fwrite(code.data(), 1, code.size(), f);
+      else fwrite(hip.data(), 1, hip.size(), f);
+      fclose(f);
+    }
+    printf("o3 record %llu: kernels %u private %u group %u\n", (unsigned long long)rec, ci.kernels,
+           ci.max_private_bytes, ci.max_group_bytes);
+    return "";
+#else
+    return "built without the assembler (ASMSIM_ASSEMBLER)";
+#endif
+  }
   if (ext) {
     std::ifstream f(ext, std::ios::binary);
     if (!f) return std::string("cannot read ") + ext;

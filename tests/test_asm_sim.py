@@ -23,6 +23,13 @@ literal pool with the LDS-staged eval row queue), plus
 random programs over the tier's
 operators and the workloads at several windows.
 
+The simulator also runs the O3 tier's compiled code (``tests/test_o3_sim_cpu.py``): SDWA selects
+on two-source ALU instructions, compares and ``v_cndmask_b32``, ``|x|`` / ``-x`` on ``v_cndmask_b32``,
+``clamp`` on ``v_sub_u32``, AGPR and SGPR spill moves, per lane.  It refuses, at parse time, every
+modifier token, select and encoding suffix that an opcode's executor does not read (SDWA elsewhere,
+destination selects, ``op_sel``, DPP controls, output modifiers, offsets and cache bits off memory
+instructions), a negative literal in a 64-bit scalar operand, and unknown instructions.
+
 Reference anchor: a candidate's verdict is ``Model.eval(And(constraints), model_completion=True)``
 (``mythril/laser/smt/model.py:45-59``) of the query ``get_model`` receives
 (``mythril/support/model.py:15-49``).
@@ -592,15 +599,22 @@ def test_asm_tier_wide_values_sim(sim_wide):
     assert total["records"] == 3 * n_q and total["ok"] == total["records"] and total["outside"] == 0, total
 
 
-def _mutants(tmp_path: Path, mutants, wide=()) -> dict:
+def _mutants(tmp_path: Path, mutants, wide=(), o3=False) -> dict:
     """Drivers built with textual edits {name: {file: (old, new)}} of their sources (no sanitizers);
     the unedited objects are compiled once and shared, everything in parallel.  The mutants named
-    in ``wide`` link the C port at -DMAXW=64 (``sim_wide``'s reference)."""
+    in ``wide`` link the C port at -DMAXW=64 (``sim_wide``'s reference).  ``o3``: the drivers also
+    hold ``jit.cpp`` and comgr's loader (-DASMSIM_ASSEMBLER), so that they compile the O3 tier's
+    kernels themselves (``tests/test_o3_sim_cpu.py``) and ``jit.cpp`` can be edited."""
     srcs = ("mythril_amd/csrc/program.cpp", "mythril_amd/csrc/jit_asm.cpp", "tests/asmsim/asmsim_main.cpp",
-            "tests/asmsim/asmsim.cpp", "oracle/bveval.c")
+            "tests/asmsim/asmsim.cpp", "oracle/bveval.c") + (("mythril_amd/csrc/jit.cpp",) if o3 else ())
     jobs, objs = [], {}
+    if o3:
+        from mythril_amd import build
+
+        build.write_prelude()
 
     def compile_(path: Path, o: Path, src: str, defs=()):
+        defs = list(defs) + (["-DASMSIM_ASSEMBLER"] if o3 else [])
         lang = ["gcc"] if src.endswith(".c") else ["g++", "-std=c++17"]
         jobs.append(subprocess.Popen(lang + ["-O1", *defs, f"-I{ROOT}", f"-I{ROOT / Path(src).parent}",
                                              "-I/opt/rocm/include", "-c", str(path), "-o", str(o)],

@@ -1,6 +1,8 @@
 """Instructions per candidate of the O3 tier's search kernel on the CPU simulator (tests/asmsim):
-the kernel is compiled as the engine compiles it (comgr, no GPU), disassembled by tools/o3dis.py and
-run over a window of 64-candidate groups with full evaluation, its hits checked against the C port.
+the simulator's driver compiles the kernel as the engine does (this tree's jit.cpp through comgr, no
+GPU: ASMSIM_O3_DUMP), tools/o3dis.py disassembles it, and the driver runs it over a window of
+64-candidate groups with full evaluation (ASMSIM_SEARCH_SOURCE_DIR), its verdicts and hits checked
+against the C port.  Exits 1 when a kernel's hits differ from the C port's or the simulator refuses it.
 VALU / SALU lane-instructions per candidate (SQ_INSTS_VALU x 64 / candidates) and LDS bank-conflict
 cycles (SQ_LDS_BANK_CONFLICT) per 64 candidates, without a GPU.
 
@@ -18,19 +20,17 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
 
-def o3_kernel(name, env, lines=False, tmp=None):
-    """(sim text, O3 source, shim lines) of workload `name`'s search kernel"""
+def o3_kernel(exe, rec, env, lines=False, tmp=None):
+    """(sim text, O3 source) of the search record's kernels, compiled by the driver `exe`"""
     tmp = tmp or tempfile.mkdtemp(prefix="o3count")
-    pre = os.path.join(tmp, name)
-    e = dict(env, MYTHGPU_JIT_DUMP=pre)
+    e = dict(env, ASMSIM_O3_DUMP=tmp)
     if lines:
         e["MYTHGPU_JIT_EXTRA"] = (e.get("MYTHGPU_JIT_EXTRA", "") + " -gline-tables-only").strip()
-    code = ("from mythril_amd import search, workloads, native\n"
-            "P, blob = search.prepare([c.raw for c in workloads.WORKLOADS[%r]()])\n"
-            "native.jit_source(P.to_bytes(), blob, compile=True)\n" % name)
-    subprocess.run([sys.executable, "-c", code], env=e, cwd=str(ROOT), check=True)
+    r = subprocess.run([str(exe)], input=rec, capture_output=True, env=e)
+    if r.returncode:
+        raise RuntimeError("O3 compile failed: " + r.stdout.decode()[-2000:] + r.stderr.decode()[-2000:])
     from tools.o3dis import convert
-    return convert(pre + ".co", lines=lines), Path(pre + ".hip").read_text()
+    return convert(os.path.join(tmp, "0.co"), lines=lines), Path(tmp, "0.hip").read_text()
 
 
 def main():
@@ -64,21 +64,22 @@ def main():
             names.append(a)
     names = names or sorted(workloads.WORKLOADS)
     exe = _cached(TPF(), sanitize=False)
-    tmp = tempfile.mkdtemp(prefix="o3count")
+    differ = 0
     for name in names:
-        text, src = o3_kernel(name, env, lines, tmp)
-        sp = os.path.join(tmp, name + ".s")
-        Path(sp).write_text(text)
+        tmp = tempfile.mkdtemp(prefix="o3count")
         P, blob = search.prepare([c.raw for c in workloads.WORKLOADS[name]()])
         rec = record(0, P.to_bytes(), blob, 7, 1 << 40, 64 * 64)
+        text, src = o3_kernel(exe, rec, env, lines, tmp)
+        Path(tmp, "0.s").write_text(text)
         r = subprocess.run([str(exe)], input=rec, capture_output=True,
-                           env=dict(env, ASMSIM_COUNT="1", ASMSIM_SEARCH_SOURCE=sp))
+                           env=dict(env, ASMSIM_COUNT="1", ASMSIM_SEARCH_SOURCE_DIR=tmp))
         out = r.stdout.decode()
         cnt = [ln for ln in out.splitlines() if ln.startswith("count record")]
         summ = [ln for ln in out.splitlines() if ln.startswith("records=")]
         ok = bool(summ) and " ok=1 " in summ[0]
+        differ += not ok
         print(name, cnt[0].split(":", 1)[1].strip() if cnt else out[-300:] + r.stderr.decode()[-300:],
-              "" if ok else "(hits DIFFER from the C port: %s)" % (summ[0] if summ else "?"))
+              "" if ok else "HITS DIFFER from the C port: %s %s" % (summ[0] if summ else "?", out[:300]))
         if lines:
             srcl = src.splitlines()
             # the comgr shim's lines come first: the kernel's signature line locates the offset
@@ -94,7 +95,8 @@ def main():
                     rows.append((float(v), n, srcl[n - 1][:140] if 0 < n <= len(srcl) else "?"))
             for v, n, t in sorted(rows, reverse=True)[:top]:
                 print("  %7.2f %5d %s" % (v, n, t))
+    return 1 if differ else 0
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())
