@@ -37,6 +37,7 @@
 #include <set>
 #include <sstream>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "jit.hpp"
@@ -267,9 +268,13 @@ class Emitter {
     }
   }
   // --- SGPR pairs ----------------------------------------------------------------------------
+  int slimit = kS1;  // the allocator's pairs end here (above: the kernel's pinned scalar literals)
   int sfree() const {  // SGPR pairs free
     int n = 0;
-    for (int r = kS0; r + 1 < kS1; r += 2) n += !sref[r];
+    for (int r = kS0; r + 1 < slimit; r += 2) n += !sref[r];
+    // the pairs the pins took count as free: they lie above every pair the unpinned emission named,
+    // and sreserve() must decide as it did there (else it would evict cached masks it never needed to)
+    n += (kS1 - slimit) / 2;
     return n;
   }
   std::function<bool()> on_spressure;  // move a Bool value's mask to its VGPR form; true if one went
@@ -285,7 +290,7 @@ class Emitter {
   }
   int salloc() {
     for (;;) {
-      for (int r = kS0; r + 1 < kS1; r += 2)
+      for (int r = kS0; r + 1 < slimit; r += 2)
         if (!sref[r]) {
           sref[r] = 1;
           sgen[r] = ++sgen_ctr;
@@ -2691,8 +2696,10 @@ struct Gen {
       for (uint32_t j = 0; j < Lc; j++) {
         const uint32_t lo = 32 * j;
         const uint32_t m = lo >= bits ? 0u : (bits - lo >= 32 ? 0xFFFFFFFFu : ((1u << (bits - lo)) - 1u));
-        if (j >= n || m == 0) E.valu("v_mov_b32_e32 " + VL(r[j]) + ", 0");
-        else if (m != 0xFFFFFFFFu) E.valu("v_and_b32_e32 " + VL(r[j]) + ", " + imm(m) + ", " + VL(r[j]));
+        if (j >= n || m == 0) {
+          note("mixed:fill");
+          E.valu("v_mov_b32_e32 " + VL(r[j]) + ", 0");
+        } else if (m != 0xFFFFFFFFu) E.valu("v_and_b32_e32 " + VL(r[j]) + ", " + imm(m) + ", " + VL(r[j]));
       }
       return r;
     }
@@ -2754,8 +2761,8 @@ struct Gen {
     if (inl(c)) {
       E.valu("v_mul_hi_u32 " + VL(d) + ", " + VL(x) + ", " + imm(c));
     } else {
-      E.salu("s_mov_b32 s41, " + hexs(c), {41});
-      E.valu("v_mul_hi_u32 " + VL(d) + ", " + VL(x) + ", s41", {41});
+      const int sc = slit(c);
+      E.valu("v_mul_hi_u32 " + VL(d) + ", " + VL(x) + ", " + S(sc), {sc});
     }
     return d;
   }
@@ -2775,8 +2782,8 @@ struct Gen {
       for (uint32_t e2 = 0; e2 < n; e2++) pack |= (G[off + e2] & m) << (e2 * w);
       const Limb sh = fresh(), d = dst(0);
       E.valu("v_mul_u32_u24_e32 " + VL(sh) + ", " + imm(w) + ", " + VL(idx));
-      E.salu("s_mov_b32 s41, " + hexs(pack), {41});
-      E.valu("v_bfe_u32 " + VL(d) + ", s41, " + VL(sh) + ", " + std::to_string(w), {41});
+      const int sc = slit(pack);
+      E.valu("v_bfe_u32 " + VL(d) + ", " + S(sc) + ", " + VL(sh) + ", " + std::to_string(w), {sc});
       drop(sh);
       r[0] = d;
       return r;
@@ -2971,16 +2978,73 @@ struct Gen {
     return e2;
   }
 
+  // What the emitter already knows where it emits a MIXED coordinate (gen_value) and the scalar
+  // literals around it:
+  //   kFactCopy     a COPY alternative whose source is generated anew (a MIXED coordinate not live
+  //                 elsewhere) has it generated into the join registers: put() then moves nothing
+  //   kFactScalars  the scalar literals a group's code loads into s40 / s41 (ALIGNED bases, clamp
+  //                 bounds, multiply-high spans, packed dictionaries, compare literals) live in SGPRs
+  //                 of their own, loaded once per kernel (pinned_kernel picks them)
+  //   kFactCascade  the alternatives' thresholds are tested as the cheapest binary tree over their
+  //                 shares, not in the blob's order
+  // MYTHGPU_JIT_ASM_NO_CLASS_FACTS=1: none (the emitted text is then what it was before these);
+  // MYTHGPU_JIT_ASM_NO_LAZY=1, which restores the text from before the guarded select arms, an
+  // earlier state still, turns them off as well;
+  // MYTHGPU_JIT_ASM_CLASS_FACTS=<mask>: a subset (development: one item's A/B)
+  static constexpr unsigned kFactCopy = 1u << 0, kFactScalars = 1u << 1, kFactCascade = 1u << 2;
+  static unsigned class_facts() {
+    static const unsigned on = [] {
+      const char* g = getenv("MYTHGPU_JIT_ASM_NO_CLASS_FACTS");
+      if ((g && g[0] == '1') || no_lazy()) return 0u;
+      const char* m = getenv("MYTHGPU_JIT_ASM_CLASS_FACTS");
+      return m ? (unsigned)strtoul(m, nullptr, 0) : ~0u;
+    }();
+    return on;
+  }
+
+  // Kernel-lifetime scalar literals.  A literal that is no inline constant reaches a VOP3 operand
+  // through an SGPR, loaded by an s_mov_b32 at every use: once per group and use.  The emission
+  // counts the sites that load one (scensus1 / scensus2: single literals, 64-bit pairs; a static count,
+  // a site in a rarely entered region weighs as one on the main path); pinned_kernel then pins
+  // the most named ones in SGPRs above every pair the allocator named (spin1 / spin2), loaded once in
+  // the prologue, and emits the kernel again.  Nothing else writes them: the allocator ends below
+  // (Emitter::slimit), and a pinned SGPR is never a VALU destination, so it needs no wait states.
+  std::map<uint32_t, int> spin1;
+  std::map<uint64_t, int> spin2;
+  std::map<uint32_t, uint32_t> scensus1;
+  std::map<uint64_t, uint32_t> scensus2;
+  // the SGPR holding literal c for the next instruction: its own, or s41 loaded here
+  int slit(uint32_t c) {
+    scensus1[c]++;
+    auto it = spin1.find(c);
+    if (it != spin1.end()) return it->second;
+    E.salu("s_mov_b32 s41, " + hexs(c), {41});
+    return 41;
+  }
+  // ... the even SGPR of the pair holding hi:lo: its own, or s[40:41] loaded here
+  int slit2(uint32_t lo, uint32_t hi) {
+    const uint64_t k = (uint64_t)hi << 32 | lo;
+    scensus2[k]++;
+    auto it = spin2.find(k);
+    if (it != spin2.end()) return it->second;
+    E.salu("s_mov_b32 s40, " + hexs(lo), {40});
+    E.salu("s_mov_b32 s41, " + hexs(hi), {41});
+    return 40;
+  }
+
   // write limbs r into the preassigned registers out (MIXED branches), releasing r
-  void put(const std::vector<Limb>& out, std::vector<Limb>& r) {
+  // (tag: the alternative's annotation, restored after the moves' own)
+  void put(const std::vector<Limb>& out, std::vector<Limb>& r, const char* tag = nullptr) {
     for (size_t j = 0; j < out.size(); j++) {
       const Limb x = j < r.size() ? r[j] : Lit(0);
       if (x == out[j]) continue;  // written in place (tgt): not a reference of its own
+      if (tag) note(x.lit() ? "mixed:fill" : "mixed:put");
       E.valu("v_mov_b32_e32 " + VL(out[j]) + ", " + src(x));
       if (j < r.size()) drop(r[j]);
     }
     for (size_t j = out.size(); j < r.size(); j++) drop(r[j]);  // limbs above the ones generated
     r.clear();
+    if (tag) note(tag);
   }
 
   // +/-(1 + (h & 1)) on the registers out, when (ws & 0xFFFF) < pdelta (scalar branch)
@@ -3065,8 +3129,8 @@ struct Gen {
         if (inl(span)) {
           E.valu("v_cmp_le_u32_e64 " + SP(ge.s) + ", " + imm(span) + ", " + VL(d0), {}, {ge.s, ge.s + 1});
         } else {
-          E.salu("s_mov_b32 s41, " + hexs(span), {41});
-          E.valu("v_cmp_le_u32_e64 " + SP(ge.s) + ", s41, " + VL(d0), {41}, {ge.s, ge.s + 1});
+          const int sc = slit(span);
+          E.valu("v_cmp_le_u32_e64 " + SP(ge.s) + ", " + S(sc) + ", " + VL(d0), {sc}, {ge.s, ge.s + 1});
         }
         if (G[r]) drop(d0);
         const Mask b2 = mop("or", bad, ge);
@@ -3118,8 +3182,8 @@ struct Gen {
       ge.k = 2;
       ge.s = E.salloc();
       const Limb d0 = vreg(dif[0]);
-      E.salu("s_mov_b32 s41, " + hexs(span), {41});
-      E.valu("v_cmp_le_u32_e64 " + SP(ge.s) + ", s41, " + VL(d0), {41}, {ge.s, ge.s + 1});
+      const int sc = slit(span);
+      E.valu("v_cmp_le_u32_e64 " + SP(ge.s) + ", " + S(sc) + ", " + VL(d0), {sc}, {ge.s, ge.s + 1});
       drop(d0);
       const Mask b2 = mop("or", bad, ge);
       E.srelease(ge);
@@ -3190,7 +3254,10 @@ struct Gen {
   // limb read, as each limb depends only on the limbs below it (carries, the UNIFORM chain) or on
   // none (dictionary entries).  A clamp reads every limb: such values are generated whole.
   // (C4: a COPY chain three MIXED levels deep whose every bit but one is fixed)
-  std::vector<Limb> gen_value(uint32_t c, uint64_t want = ~0ull) {
+  // dst (a COPY alternative's join registers): a MIXED value is generated into them where they cover
+  // every generated limb (and are even pairs where the dictionary reads pairs); those limbs come
+  // back as dst's own, not as references the caller owns (put() skips them)
+  std::vector<Limb> gen_value(uint32_t c, uint64_t want = ~0ull, const std::vector<Limb>* dst = nullptr) {
     const GenSpec sp = specs.at(c);
     const uint32_t fix = sp.kind >> 8, kind = sp.kind & 0xFFu;
     const uint32_t width = P.coord_width.at(c), Lc = Lw(width);
@@ -3209,7 +3276,13 @@ struct Gen {
         }
         CondScope cs_(*this);
         std::vector<Limb> out(Lg);
-        if (lds_pairs() && sp.p[1] && (sp.p[2] >> 16) && lds_base.count(sp.p[0])) {
+        const bool pairs = lds_pairs() && sp.p[1] && (sp.p[2] >> 16) && lds_base.count(sp.p[0]);
+        bool lent = dst && (class_facts() & kFactCopy) && dst->size() >= Lg;
+        for (uint32_t j = 0; lent && pairs && j + 1 < Lg; j += 2)
+          lent = ((*dst)[j].v & 1u) == 0 && (*dst)[j + 1].v == (*dst)[j].v + 1;
+        if (lent) {
+          for (uint32_t j = 0; j < Lg; j++) out[j] = (*dst)[j];
+        } else if (pairs) {
           // the dictionary alternative reads limb pairs straight into these: even-aligned pairs
           for (uint32_t j = 0; j < Lg; j += 2) {
             if (j + 1 < Lg) {
@@ -3244,9 +3317,19 @@ struct Gen {
           }
           put(out, u);
         };
+        const unsigned facts = class_facts();
+        // the delta and the clamp of a COPY / dictionary alternative whose limbs `zero0` are literal
+        // zeros (a delta may change them: the clamp then knows nothing); h: the dictionary's draw
+        auto tail = [&](uint64_t zero0, const Limb* h) {
+          if (sp.p[5]) delta(out, c, sp.p[5], ws, h);
+          if (h) drop(*h);
+          note("mixed:clamp");
+          finish(out, width, sp.p[6], sp.p[5] ? 0 : zero0);
+        };
         std::string next;
         bool any = false;
         auto branch = [&](uint32_t T) {  // take this alternative when ws < T << 16
+          note("mixed:class");
           if (any) {
             E.ctl("s_branch " + end);
             E.label(next);
@@ -3259,8 +3342,7 @@ struct Gen {
           }
         };
         note("mixed:key");
-        if (pc) {
-          branch(pc);
+        auto alt_copy = [&] {
           note("mixed:copy");
           std::vector<Limb> s;
           // the source's value when it is still live and whole (a copy chain's inner source may
@@ -3274,30 +3356,26 @@ struct Gen {
             s = val[it->second].l;
             for (auto& x : s) E.retain(x);
           } else {
-            s = gen_value(sp.p[3], lowmask(Lg));
+            s = gen_value(sp.p[3], lowmask(Lg), &out);
           }
           uint64_t zero = 0;  // limbs the copied value has as literal zeros (a delta may change them)
-          for (uint32_t j = 0; j < Lc && !sp.p[5]; j++)
+          for (uint32_t j = 0; j < Lc; j++)
             if (j < s.size() && s[j].lit() && s[j].v == 0) zero |= 1ull << j;
-          put(out, s);
-          if (sp.p[5]) delta(out, c, sp.p[5], ws, nullptr);
-          finish(out, width, sp.p[6], zero);
-        }
-        if (pd) {
-          branch(pc + pd);
+          put(out, s, "mixed:copy");
+          tail(zero, nullptr);
+        };
+        auto alt_dict = [&] {
           note("mixed:dict");
           const Limb h = grnd(c, 0xFFFFu);
           const Limb ix = dict_index(h, sp.p[1]);
           std::vector<Limb> dv = dict(sp.p[0], sp.p[1], width, ix, &out, Lg);
           drop(ix);
           uint64_t zero = 0;  // limbs zero in every entry (a delta may change them)
-          for (uint32_t j = 0; j < Lc && !sp.p[5]; j++)
+          for (uint32_t j = 0; j < Lc; j++)
             if (j < dv.size() && dv[j].lit() && dv[j].v == 0) zero |= 1ull << j;
-          put(out, dv);
-          if (sp.p[5]) delta(out, c, sp.p[5], ws, &h);
-          drop(h);
-          finish(out, width, sp.p[6], zero);
-        }
+          put(out, dv, "mixed:dict");
+          tail(zero, &h);
+        };
         // limbs above `bitsn` are zero in the SMALL / UNIFORM values (narrow: everything above limb 0)
         auto zeros = [&](uint32_t bitsn) {
           uint64_t z = 0;
@@ -3305,19 +3383,76 @@ struct Gen {
             if ((narrow && j > 0) || 32 * j >= bitsn) z |= 1ull << j;
           return z;
         };
-        if (ps) {
-          branch(pc + pd + ps);
+        auto alt_small = [&] {
           note("mixed:small");
           uni(small_bits);
+          note("mixed:clamp");
           finish(out, width, sp.p[6], zeros(small_bits));
+        };
+        auto alt_uniform = [&] {
+          note("mixed:uniform");
+          uni(width);
+          note("mixed:clamp");
+          finish(out, width, sp.p[6], zeros(width));
+        };
+        // the alternatives in the blob's order with their cumulative thresholds (the UNIFORM rest: all)
+        struct Alt {
+          uint32_t T;
+          std::function<void()> body;
+        };
+        std::vector<Alt> alts;
+        if (pc) alts.push_back({pc, alt_copy});
+        if (pd) alts.push_back({pc + pd, alt_dict});
+        if (ps) alts.push_back({pc + pd + ps, alt_small});
+        alts.push_back({65536u, alt_uniform});
+        const uint32_t na = (uint32_t)alts.size();
+        if ((facts & kFactCascade) && na >= 3 && alts[na - 2].T < 65536u) {
+          // Alternative i is taken when T[i-1] <= ws >> 16 < T[i]: any tree of "ws < T[k] << 16" tests
+          // picks the same one.  The tree with the fewest expected tests over the shares (four
+          // alternatives of like shares: the middle threshold first, two tests each where the blob's
+          // order takes 1, 2, 3, 3)
+          // cost[lo][hi]: expected tests (in shares) of the best tree over alternatives lo..hi; at: its root
+          uint64_t cost[4][4] = {};
+          uint32_t at[4][4] = {};
+          for (uint32_t len = 1; len < na; len++)
+            for (uint32_t lo = 0; lo + len < na; lo++) {
+              const uint32_t hi = lo + len;
+              uint64_t best = ~0ull;
+              for (uint32_t k = lo; k < hi; k++)
+                if (cost[lo][k] + cost[k + 1][hi] < best) {
+                  best = cost[lo][k] + cost[k + 1][hi];
+                  at[lo][hi] = k;
+                }
+              cost[lo][hi] = best + (alts[hi].T - (lo ? alts[lo - 1].T : 0u));
+            }
+          auto tree = [&](auto&& self, uint32_t lo, uint32_t hi) -> void {
+            if (lo == hi) {
+              alts[lo].body();
+              return;
+            }
+            const uint32_t k = at[lo][hi];
+            const std::string above = E.newlab();
+            note("mixed:class");
+            E.salu("s_cmp_lt_u32 " + S(ws) + ", " + hexs(alts[k].T << 16));
+            E.ctl("s_cbranch_scc0 " + above);
+            self(self, lo, k);
+            note("mixed:class");
+            E.ctl("s_branch " + end);
+            E.label(above);
+            self(self, k + 1, hi);
+          };
+          tree(tree, 0, na - 1);
+        } else {
+          for (uint32_t i = 0; i + 1 < na; i++) {
+            branch(alts[i].T);
+            alts[i].body();
+          }
+          if (any) {
+            E.ctl("s_branch " + end);
+            E.label(next);
+          }
+          alts[na - 1].body();
         }
-        if (any) {
-          E.ctl("s_branch " + end);
-          E.label(next);
-        }
-        note("mixed:uniform");
-        uni(width);
-        finish(out, width, sp.p[6], zeros(width));
         E.label(end);
         note("mixed:join");
         Mask wsm;
@@ -3335,7 +3470,7 @@ struct Gen {
             const uint32_t m = G[f + j], v = G[f + Lc + j];
             if (!m && !v) continue;  // (the value's bits count outside the mask too)
             if (!r[j].reg() || m == 0xFFFFFFFFu) {
-              drop(r[j]);
+              if (!(lent && j < Lg)) drop(r[j]);
               r[j] = Lit(v);
               continue;
             }
@@ -3398,14 +3533,13 @@ struct Gen {
           // base + (m << sh) over two limbs as one m * 2^sh + base (v_mad_u64_u32, the base in s[40:41])
           // instead of two shifts and a carry pair (MYTHGPU_JIT_ASM_ALIGNED_MAD=0: those)
           const uint32_t rp = E.valloc2();
-          E.salu("s_mov_b32 s40, " + hexs(G[sp.p[0]]), {40});
-          E.salu("s_mov_b32 s41, " + hexs(G[sp.p[0] + 1]), {41});
+          const int sb = slit2(G[sp.p[0]], G[sp.p[0] + 1]);
           Mask cm;
           cm.k = 2;
           cm.s = E.salloc();
           E.valu("v_mad_u64_u32 v[" + std::to_string(rp) + ":" + std::to_string(rp + 1) + "], " + SP(cm.s) + ", " + VL(m) +
-                     ", " + std::to_string(1 << sh) + ", s[40:41]",
-                 {40, 41}, {cm.s, cm.s + 1});
+                     ", " + std::to_string(1 << sh) + ", " + SP(sb),
+                 {sb, sb + 1}, {cm.s, cm.s + 1});
           E.srelease(cm);
           drop(m);
           r.assign(Lc, Lit(0));
@@ -3745,8 +3879,8 @@ struct Gen {
     if (inl(k)) {
       E.valu(std::string("v_cmp_") + op + "_u32_e64 " + SP(m.s) + ", " + VL(a) + ", " + imm(k), {}, {m.s, m.s + 1});
     } else {
-      E.salu("s_mov_b32 s41, " + hexs(k), {41});
-      E.valu(std::string("v_cmp_") + op + "_u32_e64 " + SP(m.s) + ", " + VL(a) + ", s41", {41}, {m.s, m.s + 1});
+      const int sc = slit(k);
+      E.valu(std::string("v_cmp_") + op + "_u32_e64 " + SP(m.s) + ", " + VL(a) + ", " + S(sc), {sc}, {m.s, m.s + 1});
     }
     return m;
   }
@@ -6151,8 +6285,20 @@ struct Gen {
     E.nlab = labels;
     E.vsoft = vsoft;
     census.clear();
+    scensus1.clear();
+    scensus2.clear();
     E.vfirst = kV0 + (int)pool.size();
     E.vhigh = E.vfirst;
+    // the pinned scalar literals sit above the allocator's pairs
+    int spin_top = 0;
+    for (const auto& kv : spin1) {
+      E.slimit = std::min(E.slimit, kv.second & ~1);
+      spin_top = std::max(spin_top, kv.second + 1);
+    }
+    for (const auto& kv : spin2) {
+      E.slimit = std::min(E.slimit, kv.second);
+      spin_top = std::max(spin_top, kv.second + 2);
+    }
     val.assign(P.vwidth.size(), Val{});
     cval.clear();
     auto& o = E.o;
@@ -6194,6 +6340,11 @@ struct Gen {
     E.salu("s_mov_b64 s[30:31], -1", {30, 31});
     E.salu("s_mov_b64 s[32:33], 0", {32, 33});
     for (const auto& kv : pool) E.valu("v_mov_b32_e32 " + V((uint32_t)kv.second) + ", " + imm(kv.first));
+    for (const auto& kv : spin1) E.salu("s_mov_b32 " + S(kv.second) + ", " + hexs(kv.first), {kv.second});
+    for (const auto& kv : spin2) {
+      E.salu("s_mov_b32 " + S(kv.second) + ", " + hexs((uint32_t)kv.first), {kv.second});
+      E.salu("s_mov_b32 " + S(kv.second + 1) + ", " + hexs((uint32_t)(kv.first >> 32)), {kv.second + 1});
+    }
     // the lane half of the lane key: fmix64(lane ^ sk)
     E.valu("v_xor_b32_e32 v2, s12, v1", {12});
     E.valu("v_mov_b32_e32 v3, s13", {13});
@@ -6442,7 +6593,7 @@ struct Gen {
       const char* g = getenv("MYTHGPU_JIT_ASM_DIAG_VGPRS");
       return g ? std::max(0, std::min(256, atoi(g))) : 0;
     }();
-    const int nv = std::max({E.vhigh, kV0, diag_vgprs}), ns = std::max(E.shigh, 56);
+    const int nv = std::max({E.vhigh, kV0, diag_vgprs}), ns = std::max({E.shigh, 56, spin_top});
     const int accum = (nv + 3) / 4 * 4;
     o << "  .section .rodata,\"a\",@progbits\n  .p2align 6, 0x0\n  .amdhsa_kernel " << name << "\n"
       << "    .amdhsa_group_segment_fixed_size " << lds_words * 4 << "\n    .amdhsa_private_segment_fixed_size 0\n"
@@ -6457,8 +6608,10 @@ struct Gen {
     meta_lds = lds_words * 4;
     meta_vgpr[name] = nv;
     meta_sgpr[name] = ns + 6;
+    meta_shigh = E.shigh;
     return o.str();
   }
+  int meta_shigh = 0;  // the last kernel()'s highest allocated SGPR pair's end
   std::map<std::string, int> meta_vgpr, meta_sgpr;
   uint32_t meta_lds = 0;
 };
@@ -6702,6 +6855,44 @@ int jit_asm_source(const Lowered& P, const std::vector<GenSpec>& specs, const st
   }
 }
 
+// The kernel as Gen::kernel emits it, then once more with the scalar literals most sites load pinned
+// (Gen::slit) in the SGPRs above the highest pair that emission allocated: the allocator's range in
+// the second emission ends where the first one's use did, so the pins change no allocation, evict no
+// cached mask and leave every conditional region the pairs it reserved.  kPinTop keeps the kernel's
+// SGPRs (with VCC and the reserved six) within the 96 that eight waves per SIMD share out of 800.
+constexpr int kPinTop = 88, kPinMost = 16;
+static std::string pinned_kernel(Gen& g, const char* name) {
+  g.spin1.clear();
+  g.spin2.clear();
+  const auto labels0 = g.labels;
+  std::string ks = g.kernel(name);
+  if (!(Gen::class_facts() & Gen::kFactScalars)) return ks;
+  std::vector<std::tuple<uint32_t, int, uint64_t>> by;  // (loads, registers, literal)
+  for (const auto& kv : g.scensus1) by.push_back({kv.second, 1, kv.first});
+  for (const auto& kv : g.scensus2) by.push_back({2 * kv.second, 2, kv.first});
+  std::sort(by.begin(), by.end(), [](const auto& a, const auto& b) {
+    return std::get<0>(a) != std::get<0>(b) ? std::get<0>(a) > std::get<0>(b) : a < b;
+  });
+  // (not below s56: the group's closing code names s44 .. s55 itself, past the allocator)
+  const int base = (std::max(g.meta_shigh, 56) + 1) & ~1;
+  int room = std::min(kPinMost, kPinTop - base);
+  std::vector<uint64_t> ones, pairs;
+  for (const auto& t : by) {
+    if (std::get<1>(t) > room) continue;
+    room -= std::get<1>(t);
+    (std::get<1>(t) == 2 ? pairs : ones).push_back(std::get<2>(t));
+  }
+  if (ones.empty() && pairs.empty()) return ks;
+  int at = base;  // the pairs first: even SGPRs
+  for (uint64_t k : pairs) {
+    g.spin2[k] = at;
+    at += 2;
+  }
+  for (uint64_t k : ones) g.spin1[(uint32_t)k] = at++;
+  g.labels = labels0;
+  return g.kernel(name);
+}
+
 static std::string search_kernels(Gen& g, uint32_t kernels, bool strict) {
   std::ostringstream o;
   {
@@ -6756,13 +6947,13 @@ static std::string search_kernels(Gen& g, uint32_t kernels, bool strict) {
       const int room = std::max(0, std::min(96, g.vsoft) - v0);
       for (size_t i = 0; i < by.size() && (int)i < room; i++) g.pool[by[i].second] = kV0 + (int)i;
       g.labels = 0;
-      ks = g.kernel("mgj_search");
+      ks = pinned_kernel(g, "mgj_search");
     }
     o << ks;
     const bool with_gen = (kernels & JIT_GEN) != 0;
     if (with_gen) {
       g.gen_kernel = true;
-      o << g.kernel("mgj_gen");
+      o << pinned_kernel(g, "mgj_gen");
     }
     o << metadata(g.meta_vgpr, g.meta_sgpr, with_gen, g.meta_lds);
   }

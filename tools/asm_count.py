@@ -2,7 +2,9 @@
 every workload, a full-evaluation launch (no early exit) over a window of 64-candidate groups, VALU
 and SALU lane-instructions per candidate (the PMC's SQ_INSTS_VALU x 64 / candidates, without a GPU).
 
-  python tools/asm_count.py [workload ...] [--env K=V ...]   (ASMSIM_SEED / ASMSIM_START / ASMSIM_GROUPS: the window)"""
+  python tools/asm_count.py [workload ...] [--env K=V ...]   (ASMSIM_SEED / ASMSIM_START / ASMSIM_GROUPS: the window;
+   ASMSIM_JSONL=file ASMSIM_LABEL=name: append each workload's counts to a JSON-lines file)"""
+import json
 import os
 import random
 import re
@@ -55,6 +57,27 @@ def main():
             m = re.match(r"vcode (\d+) lazy:select x(\d+)$", t)
             if m and int(m.group(2)):
                 print(f"  guard closing at vcode {m.group(1)}: region taken by {v / int(m.group(2)):.3f} of the groups")
+        # the MIXED generator's phases over all coordinates and emission sites: VALU and SALU per group
+        # (a phase emitted in several alternatives, or per limb, is one tag per site above)
+        mixed = {}
+        for v, sv, t in tags:
+            m = re.match(r"vcode \d+ (mixed:\w+)$", t)
+            if m:
+                a = mixed.setdefault(m.group(1), [0.0, 0.0])
+                a[0] += v
+                a[1] += sv
+        if mixed:
+            print("  MIXED phases (VALU, SALU per group): " +
+                  "  ".join(f"{k[6:]} {a[0]:.2f}/{a[1]:.2f}" for k, a in sorted(mixed.items())))
+        if env.get("ASMSIM_JSONL") and line:
+            words = line[0].split(":", 1)[1].split()
+            rec = {"workload": name, "label": env.get("ASMSIM_LABEL", ""), "seed": int(env.get("ASMSIM_SEED", "7"), 0),
+                   "start": int(env.get("ASMSIM_START", str(1 << 40)), 0), "groups": int(env.get("ASMSIM_GROUPS", "64"), 0),
+                   "equals_c_port": ok,
+                   "per_group": {words[i]: float(words[i + 1]) for i in range(0, len(words) - 2, 2)},
+                   "mixed_phases": {k[6:]: {"valu": round(a[0], 2), "salu": round(a[1], 2)} for k, a in sorted(mixed.items())}}
+            with open(env["ASMSIM_JSONL"], "a") as f:
+                f.write(json.dumps(rec) + "\n")
         key = (lambda x: x[1]) if env.get("ASMSIM_SORT") == "salu" else (lambda x: x[0])
         for v, sv, t in sorted(tags, key=key, reverse=True)[:int(env.get("ASMSIM_TOP", "40"))]:
             print(f"  {v:8.2f} {sv:8.2f}  {t}")

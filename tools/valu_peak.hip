@@ -8,11 +8,13 @@
 // v_fma_f32 is included to calibrate against the guide's measured 2 cycles.
 //
 // Output: one JSON line per (op, waves/SIMD).  Pins the "peak" for roofline.frac.
+// Usage: valu_peak [text]   (only the ops whose name holds text, e.g. v_mov)
 // Build: hipcc --offload-arch=gfx950 -O3 -o tools/valu_peak tools/valu_peak.hip
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #define CHK(x)                                                                  \
@@ -29,24 +31,26 @@ constexpr int NCHAIN = 8;
 
 enum Op {
   FMA_F32 = 0, ADD, XOR, LSHR, ADD_LIT, ADDC, SUBB, CND_VCC, CND_SGPR, CMP, MULLO, MULHI, MAD64, LSHLOR, ADD3,
-  OR3, ALIGNBIT, BFE, PERM, NOPS
+  OR3, ALIGNBIT, BFE, PERM, MOV32, MOV64, NOPS
 };
 static const char* kNames[NOPS] = {
     "v_fma_f32", "v_add_u32", "v_xor_b32", "v_lshrrev_b32", "v_add_u32 (literal)", "v_add_co_u32+v_addc_co_u32",
     "v_sub_co_u32+v_subb_co_u32", "v_cndmask_b32 (vcc)", "v_cndmask_b32_e64 (sgpr mask)", "v_cmp_lt_u32_e64",
     "v_mul_lo_u32", "v_mul_hi_u32", "v_mad_u64_u32", "v_lshl_or_b32", "v_add3_u32", "v_or3_b32",
-    "v_alignbit_b32", "v_bfe_u32", "v_perm_b32"};
-static const int kInstr[NOPS] = {1, 1, 1, 1, 1, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
+    "v_alignbit_b32", "v_bfe_u32", "v_perm_b32", "v_mov_b32 (0)", "v_mov_b64 (0)"};
+static const int kInstr[NOPS] = {1, 1, 1, 1, 1, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
 
 template <int OP>
 __global__ void __launch_bounds__(64) k_valu(uint32_t* out, unsigned long long* cyc, uint32_t seed) {
   uint32_t a[NCHAIN], b[NCHAIN];
   float f[NCHAIN];
+  uint64_t p64[NCHAIN];
 #pragma unroll
   for (int c = 0; c < NCHAIN; c++) {
     a[c] = seed * (threadIdx.x + 1) + c;
     b[c] = seed ^ (c * 0x9E3779B9u + threadIdx.x);
     f[c] = (float)a[c];
+    p64[c] = ((uint64_t)b[c] << 32) | a[c];
   }
   const uint32_t k = seed | 1u;
   const float fk = 1.0001f;
@@ -109,15 +113,23 @@ __global__ void __launch_bounds__(64) k_valu(uint32_t* out, unsigned long long* 
         asm volatile("v_alignbit_b32 %0, %0, %1, 7" : "+v"(a[c]) : "v"(b[c]));
       } else if constexpr (OP == BFE) {
         asm volatile("v_bfe_u32 %0, %0, 3, 17" : "+v"(a[c]));
-      } else {
+      } else if constexpr (OP == PERM) {
         asm volatile("v_perm_b32 %0, %0, %1, %2" : "+v"(a[c]) : "v"(b[c]), "v"(k));
+      } else if constexpr (OP == MOV32) {
+        // a literal fill of one limb (the MIXED alternatives' zero limbs); "+v" keeps the eight
+        // destinations apart, as the emitter's fills are (write-only outputs would share one register
+        // and the compiler would put an s_nop between the writes)
+        asm volatile("v_mov_b32 %0, 0" : "+v"(a[c]));
+      } else {
+        // ... and of an even-aligned limb pair in one instruction: per limb, half this row's cost
+        asm volatile("v_mov_b64 %0, 0" : "+v"(p64[c]));
       }
     }
   }
   const unsigned long long t1 = __builtin_amdgcn_s_memtime();
   uint32_t s = 0;
 #pragma unroll
-  for (int c = 0; c < NCHAIN; c++) s ^= a[c] ^ b[c] ^ __float_as_uint(f[c]);
+  for (int c = 0; c < NCHAIN; c++) s ^= a[c] ^ b[c] ^ __float_as_uint(f[c]) ^ (uint32_t)p64[c] ^ (uint32_t)(p64[c] >> 32);
   out[blockIdx.x * 64 + threadIdx.x] = s;
   if (threadIdx.x == 0) cyc[blockIdx.x] = t1 - t0;
 }
@@ -151,15 +163,18 @@ static void run(int cus, uint32_t* d, unsigned long long* dc, hipEvent_t e0, hip
   }
 }
 
+static const char* g_only = nullptr;  // argv[1]: only the ops whose name holds this text
+
 template <int OP>
 static void run_all(int cus, uint32_t* d, unsigned long long* dc, hipEvent_t e0, hipEvent_t e1, double ghz) {
   if constexpr (OP < NOPS) {
-    run<OP>(cus, d, dc, e0, e1, ghz);
+    if (!g_only || strstr(kNames[OP], g_only)) run<OP>(cus, d, dc, e0, e1, ghz);
     run_all<OP + 1>(cus, d, dc, e0, e1, ghz);
   }
 }
 
-int main() {
+int main(int argc, char** argv) {
+  if (argc > 1) g_only = argv[1];
   hipDeviceProp_t p;
   CHK(hipGetDeviceProperties(&p, 0));
   const int cus = p.multiProcessorCount;
