@@ -114,6 +114,60 @@ std::string VP(uint32_t r) { return "v[" + std::to_string(r) + ":" + std::to_str
 constexpr int kV0 = 12;
 constexpr int kS0 = 44, kS1 = 100;
 
+// An upper bound on the dwords the assembler makes of emitted text, every instruction taken at its
+// longest encoding: one dword only for what is provably one — a VOP1/VOP2/VOPC spelt _e32, or one of
+// the SALU mnemonics below, with no operand that could be a 32-bit literal (a number outside the
+// inline range -16 .. 64, or anything with a '.' or an 'x') — and two for everything else (VOP3, SDWA,
+// SMEM, DS, global; gfx950 has no longer encoding).  A loop's branches reach +-32,767 dwords
+// (simm16): the emitter refuses a body past that itself, comgr's answer would be an error.
+constexpr uint32_t kBranchDwords = 32767;
+uint32_t longest_dwords(const std::string& text) {
+  static const char* const kSalu1[] = {"s_mov_", "s_cmp_", "s_add_", "s_addc_", "s_sub_", "s_subb_", "s_and_", "s_andn2_",
+                                       "s_or_", "s_orn2_", "s_xor_", "s_not_", "s_lshl_", "s_lshr_", "s_ashr_", "s_mul_",
+                                       "s_min_", "s_max_", "s_cselect_", "s_bfe_", "s_bcnt1_", "s_ff1_", "s_flbit_",
+                                       "s_nop", "s_waitcnt", "s_branch", "s_cbranch_", "s_endpgm", "s_barrier"};
+  uint32_t dwords = 0;
+  size_t at = 0;
+  while (at < text.size()) {
+    size_t nl = text.find('\n', at);
+    if (nl == std::string::npos) nl = text.size();
+    size_t b = at;
+    while (b < nl && (text[b] == ' ' || text[b] == '\t')) b++;
+    const std::string line = text.substr(b, nl - b);
+    at = nl + 1;
+    if (line.empty() || line[0] == ';' || line[0] == '.' || line.back() == ':') continue;  // comment, directive, label
+    const size_t sp = line.find(' ');
+    const std::string mn = line.substr(0, sp);
+    bool one = mn.size() > 4 && mn.compare(mn.size() - 4, 4, "_e32") == 0;
+    if (!one && mn.compare(0, 2, "s_") == 0)
+      for (const char* p : kSalu1) one = one || mn.compare(0, strlen(p), p) == 0;
+    const bool sopp = mn == "s_nop" || mn == "s_waitcnt" || mn == "s_branch" || mn.compare(0, 10, "s_cbranch_") == 0;
+    if (one && !sopp && sp != std::string::npos) {  // (a SOPP's operand lies in its one dword)
+      size_t q = sp;
+      while (one && q < line.size()) {
+        while (q < line.size() && (line[q] == ' ' || line[q] == ',')) q++;
+        size_t e = q;
+        while (e < line.size() && line[e] != ' ' && line[e] != ',') e++;
+        const std::string tok = line.substr(q, e - q);
+        q = e;
+        if (tok.empty() || tok[0] == ';') break;
+        const bool num = tok[0] == '-' || (tok[0] >= '0' && tok[0] <= '9');
+        if (!num) {  // a register name; any other word (a symbol patched in later) may stand for a literal
+          one = tok[0] == 'v' || tok[0] == 's' || tok == "exec" || tok == "exec_lo" || tok == "exec_hi" || tok == "m0";
+          continue;
+        }
+        if (tok.find_first_of(".xX") != std::string::npos || tok.size() > 3) one = false;
+        else {
+          const int v = atoi(tok.c_str());
+          one = v >= -16 && v <= 64;
+        }
+      }
+    }
+    dwords += one ? 1u : 2u;
+  }
+  return dwords;
+}
+
 class Emitter {
  public:
   std::ostringstream o;
@@ -3608,9 +3662,10 @@ struct Gen {
   // kernel (the O3 kernel then).  Off unless the kernel fails without (jit_asm_source).
   // Slot layout, lane-major: lane l's slot k at s35 + 4 (S l + k), S = spill_stride() (odd, so the
   // 64 lanes of one access fall in distinct banks), one 16-bit ds offset of 4 k reaching every slot.
-  // The slots of a workgroup's waves must fit the 160 KiB of LDS: at most 159 per wave with four
-  // working waves; a read-back that needs more (VMTests' expXY: 63 live 256-bit keys) runs `solo` —
-  // one working wave per 256-lane workgroup, the other three exit at once — with up to 639.
+  // The slots of a workgroup's waves must fit the 160 KiB of LDS, at the odd stride: at most 159 per
+  // wave with four working waves (slots 0 .. 158; a 160th would make the stride 161); a read-back that
+  // needs more (VMTests' expXY: 63 live 256-bit keys) runs `solo` — one working wave per 256-lane
+  // workgroup, the other three exit at once — with up to 639 (slots 0 .. 638).
   bool spill_on = false;
   bool solo = false;
   uint32_t spill_stride() const { return spill_hwm | 1u; }
@@ -3659,7 +3714,9 @@ struct Gen {
       if (!x.l[j].reg()) continue;
       uint32_t sl = 0;
       while (sl < slot_busy.size() && slot_busy[sl]) sl++;
-      if ((sl | 1u) > spill_cap()) fail("out of VGPRs (spill slots)");
+      // the stride this slot would give (spill_hwm = sl + 1, made odd), not the slot itself: slot 159
+      // makes 161 slots per wave, 4 x 161 x 256 B = 164,864 B of the CU's 163,840
+      if (((sl + 1u) | 1u) > spill_cap()) fail("out of VGPRs (spill slots)");
       if (sl == slot_busy.size()) slot_busy.push_back(0);
       slot_busy[sl] = 1;
       spill_hwm = std::max(spill_hwm, sl + 1);
@@ -6165,8 +6222,10 @@ struct Gen {
       E.salu("s_add_u32 s31, s31, -1", {31});
       E.salu("s_lshr_b32 s32, s17, 6", {32});
     }
+    std::streamoff span_from = -1;  // the text the group loop's branches must span (from the farthest one)
     if (!solo) {
       E.salu("s_cmp_lt_u32 s16, s8");
+      span_from = (std::streamoff)o.tellp();
       E.ctl("s_cbranch_scc0 " + exit_);
     }
     E.valu("v_add_u32_e32 v3, s16, v1", {16});
@@ -6239,6 +6298,12 @@ struct Gen {
     if (!solo) {
       E.salu("s_add_u32 s16, s16, s17", {16});
       E.ctl("s_branch " + loop);
+      // the first exit branch reaches forward over the first group's loads and the whole body, the
+      // closing branch back over the body: neither may be past a branch's 16 signed bits of dwords
+      const uint32_t span = longest_dwords(o.str().substr((size_t)span_from));
+      if (span > kBranchDwords)
+        fail("the group loop's body may exceed the branch range (at most " + std::to_string(span) + " dwords, a branch spans " +
+             std::to_string(kBranchDwords) + ")");
     }
     E.label(exit_);
     E.ctl("s_waitcnt vmcnt(0)");  // the last iteration's loads for a group past n
@@ -6798,7 +6863,10 @@ int jit_asm_source(const Lowered& P, const std::vector<GenSpec>& specs, const st
       // out of VGPRs at every queue depth: once more with spills to LDS (Gen::spill_one), a depth-8
       // register queue and the caches bounded by all 256 registers.  MYTHGPU_JIT_ASM_NO_SPILL=1: refuse
       const char* ns = getenv("MYTHGPU_JIT_ASM_NO_SPILL");
-      if ((ns && ns[0] == '1') || f.why.find("out of VGPRs") == std::string::npos) throw;
+      // A kernel that fits its registers but whose body is past the group loop's branch range takes the
+      // same road to the loop-free solo kernel (whose spiller then has nothing to do)
+      const bool range = f.why.find("branch range") != std::string::npos;
+      if (!range && ((ns && ns[0] == '1') || f.why.find("out of VGPRs") == std::string::npos)) throw;
       Gen g2(P, specs, gconsts);
       g2.eval_kernel = true;
       g2.tiled = (kernels & JIT_EVAL_TILED) || getenv("MYTHGPU_JIT_ASM_TILED");
@@ -6814,8 +6882,9 @@ int jit_asm_source(const Lowered& P, const std::vector<GenSpec>& specs, const st
       try {
         ks = g2.kernel_eval("mgj_eval");
       } catch (const AsmFail& f2) {
-        // more slots than four waves' LDS holds: one working wave per workgroup (Gen::solo)
-        if (f2.why.find("spill slots") == std::string::npos) throw;
+        // more slots than four waves' LDS holds, or a body the group loop's branches cannot span: one
+        // working wave per workgroup (Gen::solo: up to 639 slots, one group per workgroup and no loop)
+        if (f2.why.find("spill slots") == std::string::npos && f2.why.find("branch range") == std::string::npos) throw;
         g2.solo = true;
         g2.labels = 0;
         ks = g2.kernel_eval("mgj_eval");

@@ -240,6 +240,10 @@ void admit(const Ins& ins, unsigned seen) {
   if ((seen & M_OFFSET) && !(vmem || lds)) no("offset:");
   if ((seen & M_OFFSET) && (op == OP_ds_read2_b32 || op == OP_ds_write2_b32)) no("offset: (offset0: / offset1: here)");
   if ((seen & M_OFFSET01) && op != OP_ds_read2_b32 && op != OP_ds_write2_b32) no("offset0: / offset1:");
+  // a DS instruction's offset is 16 unsigned bits (offset0 / offset1: 8 each); the assembler refuses more
+  if (lds && (ins.offset < 0 || ins.offset > 0xFFFF)) no("an offset outside 16 unsigned bits");
+  if (lds && (ins.offset0 < 0 || ins.offset0 > 0xFF || ins.offset1 < 0 || ins.offset1 > 0xFF))
+    no("an offset0 / offset1 outside 8 unsigned bits");
   if ((seen & M_CACHE) && !vmem) no("a cache policy bit");
   if ((seen & M_BITOP3) && op != OP_v_bitop3_b32 && op != OP_v_bitop3_b16) no("bitop3:");
   if ((seen & M_OPSEL) && op != OP_v_pk_mov_b32) no("op_sel");
@@ -293,8 +297,14 @@ Module parse(const std::string& text) {
         continue;
       }
       if (t.rfind(".amdhsa_kernel ", 0) == 0) cur_kd = trim(t.substr(15));
-      if (t.rfind(".amdhsa_group_segment_fixed_size", 0) == 0 && !cur_kd.empty())
-        m.kernels[cur_kd].lds_bytes = (uint32_t)atol(trim(t.substr(32)).c_str());
+      if (t.rfind(".amdhsa_group_segment_fixed_size", 0) == 0 && !cur_kd.empty()) {
+        // the hardware's limit, as the engine's load gate has it: a gfx950 CU holds 160 KiB of LDS
+        const long bytes = atol(trim(t.substr(32)).c_str());
+        if (bytes < 0 || bytes > kLdsPerCu)
+          err("kernel " + cur_kd + " declares " + std::to_string(bytes) + " B of LDS (a gfx950 CU has " +
+              std::to_string(kLdsPerCu) + ")");
+        m.kernels[cur_kd].lds_bytes = (uint32_t)bytes;
+      }
       if (t == ".end_amdhsa_kernel") cur_kd.clear();
       if (t.back() == ':' && t.find(' ') == std::string::npos) labels[t.substr(0, t.size() - 1)] = (int)m.code.size();
       continue;

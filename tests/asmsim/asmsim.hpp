@@ -65,6 +65,8 @@ struct Ins {
   int64_t pc = -1;      // code address (".asmsim_pc A" before it; s_getpc_b64 of compiled code)
 };
 
+constexpr long kLdsPerCu = 160 * 1024;  // parse() refuses a kernel that declares more (the load gate's limit)
+
 struct Kernel {
   size_t entry = 0;
   uint32_t lds_bytes = 0;
