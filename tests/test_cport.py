@@ -31,11 +31,34 @@ def test_cport_generator_matches_python_oracle_on_workloads(name):
     P = ssa.flatten(roots)
     g = search.default_generator(P)
     first, hits, ver = cport.search(P.to_bytes(), g.blob(), 7, 1000, 64, threads=2, verdicts=True)
-    # the same candidates through explicit coordinates: regenerate with the C port's
-    # generator via a 1-candidate search per coordinate is not exposed, so check the
-    # verdict count only against eval of an independent explicit sample
     assert ver.shape == (64,)
     assert hits == int(ver.sum())
+    _against_the_oracle(P, roots, g.blob(), 7, 1000, ver)
+
+
+def _against_the_oracle(P, roots, blob, seed, start, ver):
+    """Each verdict equals the Python oracle's on the coordinates the GEN3 restatement
+    (``tests/gen3_ref.py``, big integers) generates for that candidate."""
+    from tests import gen3_ref as R
+
+    specs, consts = R.split_blob(blob)
+    widths = [c.width for c in P.coords]
+    for q in range(len(ver)):
+        m = model_from_coordinates(P, R.gen_values(specs, consts, widths, seed, start + q))
+        assert ver[q] == int(all(evaluate(r, m) == 1 for r in roots)), (start + q,)
+
+
+@pytest.mark.parametrize("name", ["w256_div_mg_11", "w256_exp_mixed_L33_lane0", "w64_div_signed_edges", "w33_shift_mixed"])
+def test_cport_generator_matches_python_oracle_on_wave_cases(name):
+    """The same on generator-form cases of the wave table (``tests/wave_op_cases.py``), whose windows
+    hold hits and misses: both windows, first hit and hit count included."""
+    from tests import wave_op_cases as W
+
+    c = W.gen_case(name)
+    for start in W.GEN_STARTS:
+        first, hits, ver = cport.search(c.pb, c.blob, c.seed, start, 256, threads=2, verdicts=True)
+        assert 0 < hits < 256 and hits == int(ver.sum()) and first == start + int(np.flatnonzero(ver)[0])
+        _against_the_oracle(c.P, c.roots, c.blob, c.seed, start, ver)
 
 
 def test_workload_selectors_are_keccak_of_signatures():
